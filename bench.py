@@ -8,8 +8,14 @@ i.e. STRONG scaling: the tree (2,573,652 nodes, sol 2,648, makespan 1377) is the
 same at every N. Each step's tree/sol/makespan is checked against the golden
 values, so a skipped or truncated search fails instead of reporting a number.
 
-After the timed headline loop the other BASELINE multi-GPU configs run in the same
-job (all ranks cooperating, same runtime), unless --no-extras:
+A plain run does only what the headline needs: set-up, warm-up, the timed steps, the
+JSON line. --dump-outputs DIR then writes what the last timed step returned to its
+caller as DIR/solve.npy (float64: makespan, tree, sol, complete), so that two builds
+can be compared output for output; the instance is regenerated from its seed, so the
+inputs are the same in every run.
+
+With --full the other BASELINE multi-GPU configs run after the timed headline loop in
+the same job (all ranks cooperating, same runtime), unless --no-extras:
   * ta021 (20x20) LB1_d, one complete solve: makespan 2297 and the -u 1 tree
     (260,069,628,524 nodes, sol 14,963,858 — deterministic at every N) are checked;
   * ta056 (50x20) LB2, a fixed time box (--box-s, default 10 s): explored nodes/s
@@ -20,7 +26,7 @@ They become fields of the same single JSON line ("extras"). An extra that fails 
 reported there (and on stderr) and the headline line is still printed; a watchdog
 (--extras-timeout) prints the line and ends every rank if an extra hangs.
 
-Launch: python bench.py [--gpus 1 --steps K --warmup W]
+Launch: python bench.py [--gpus 1 --steps K --warmup W] [--dump-outputs DIR] [--full]
         python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
                --master-port P bench.py --gpus N --steps K --warmup W
 Rank 0 prints exactly one JSON line on stdout; everything else goes to stderr.
@@ -95,8 +101,12 @@ def main() -> int:
     ap.add_argument("--comm", choices=["nccl", "gloo"], default="nccl",
                     help="process group for node transfers (gloo: ranks may share one GPU, for tests)")
     ap.add_argument("--device", type=int, default=None, help="GPU of this rank (default LOCAL_RANK)")
-    ap.add_argument("--no-extras", action="store_true", help="headline only (no ta021 / ta056 runs)")
-    ap.add_argument("--extras", default="ta021,ta056,nq17", help="comma list of extras to run")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned as DIR/solve.npy (rank 0)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline also run the extras (ta021 / ta056 / N-Queens runs)")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: headline only after all")
+    ap.add_argument("--extras", default="ta021,ta056,nq17", help="comma list of extras to run with --full")
     ap.add_argument("--box-s", type=float, default=10.0, help="ta056 LB2 time box (seconds)")
     ap.add_argument("--extras-timeout", type=float, default=300.0,
                     help="watchdog: print the line and end every rank after this many seconds of extras")
@@ -165,6 +175,14 @@ def main() -> int:
     last = solver.result(*raw)
     dt = float(comm.allgather_f64([dt_local]).max())
     value = tree / dt
+    if a.dump_outputs and comm.rank == 0:
+        import numpy as np
+
+        # the global values solve_raw returned in the last timed step (its timers and the
+        # round count of a work-sharing run differ from run to run and stay in the line)
+        os.makedirs(a.dump_outputs, exist_ok=True)
+        np.save(os.path.join(a.dump_outputs, "solve.npy"),
+                np.array([raw[0], raw[1], raw[2], raw[4]], dtype=np.float64))
     if comm.rank == 0:
         log(f"last step: elapsed {last.elapsed * 1e3:.3f} ms, init {last.t_init * 1e3:.3f} ms, "
             f"search {last.t_search * 1e3:.3f} ms, rounds {last.extra.get('rounds')}, "
@@ -199,7 +217,7 @@ def main() -> int:
     }
     del solver, engine
 
-    if not a.no_extras:
+    if a.full and not a.no_extras:
         extras: dict = {}
         rec["extras"] = extras
 

@@ -14,12 +14,12 @@ for step in "$@"; do
         > "$out/gpu_tests.log" 2>&1 || { tail -30 "$out/gpu_tests.log"; exit 1; }
       tail -3 "$out/gpu_tests.log" ;;
     bench1)
-      timeout -k 10 180 python bench.py --steps 20 --warmup 5 > "$out/bench_n1.json" 2> "$out/bench_n1.err" \
+      timeout -k 10 180 python bench.py --steps 20 --warmup 5 --full > "$out/bench_n1.json" 2> "$out/bench_n1.err" \
         || { tail -20 "$out/bench_n1.err"; exit 1; }
       cat "$out/bench_n1.json" ;;
     bench2shared)
       timeout -k 10 180 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 \
-        --master-port 29533 bench.py --gpus 2 --steps 20 --warmup 5 --comm gloo --device 0 \
+        --master-port 29533 bench.py --gpus 2 --steps 20 --warmup 5 --full --comm gloo --device 0 \
         > "$out/bench_n2_shared.json" 2> "$out/bench_n2_shared.err" || { tail -20 "$out/bench_n2_shared.err"; exit 1; }
       cat "$out/bench_n2_shared.json"; grep "last step" "$out/bench_n2_shared.err" ;;
     lb2:*)  # lb2:<seconds>[@ENV=V,...]

@@ -96,7 +96,7 @@ def test_bench_extras_cpu_gloo():
     # LB1_d solve, a 0.5-s ta056 LB2 box, N-Queens N=11 for N=17)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", str(free_port()), "bench.py", "--gpus", "2",
-           "--steps", "1", "--warmup", "0", "--backend", "cpu", "--comm", "gloo", "--extra-inst-lb1d", "14",
+           "--steps", "1", "--warmup", "0", "--backend", "cpu", "--comm", "gloo", "--full", "--extra-inst-lb1d", "14",
            "--box-s", "0.5", "--extra-queens-n", "11"]
     out = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
@@ -144,11 +144,26 @@ def test_bench_runs_without_transfers_after_failed_preflight():
 
 def test_bench_extras_failure_still_prints_headline():
     # an extra that fails is reported in the line; the headline is printed regardless
-    cmd = [sys.executable, "bench.py", "--steps", "1", "--warmup", "0", "--backend", "cpu", "--extras", "nosuch"]
+    cmd = [sys.executable, "bench.py", "--steps", "1", "--warmup", "0", "--backend", "cpu", "--full", "--extras",
+           "nosuch"]
     out = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=300)
     assert out.returncode == 0, out.stderr[-2000:]
     rec = json.loads([x for x in out.stdout.splitlines() if x.startswith("{")][0])
     assert rec["value"] > 0 and rec["extras"]["nosuch"] == {"error": "unknown extra"}
+
+
+def test_bench_plain_run_is_headline_only_and_dumps_outputs(tmp_path):
+    # without --full: no extras in the line; --dump-outputs writes the last step's result
+    cmd = [sys.executable, "bench.py", "--gpus", "1", "--steps", "2", "--warmup", "1", "--backend", "cpu",
+           "--dump-outputs", str(tmp_path / "out")]
+    out = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=300)
+    assert out.returncode == 0, out.stderr[-2000:]
+    rec = json.loads([x for x in out.stdout.splitlines() if x.startswith("{")][0])
+    assert "extras" not in rec and rec["steps"] == 2 and rec["ms_per_step"] > 0
+    assert abs(rec["value"] * rec["ms_per_step"] * 1e-3 - GOLD[0]) < 1e-3 * GOLD[0]
+    assert os.listdir(tmp_path / "out") == ["solve.npy"]
+    got = np.load(tmp_path / "out" / "solve.npy")
+    assert got.dtype == np.float64 and got.tolist() == [GOLD[2], GOLD[0], GOLD[1], 1.0]
 
 
 @pytest.mark.parametrize("world,problem", [(1, "pfsp"), (2, "pfsp"), (2, "nqueens")])
