@@ -399,6 +399,35 @@ PYBIND11_MODULE(_tts_hip, m) {
       "A complete front-kernel engine solve from these (front-layout) nodes with probe records on: every child "
       "bound of every iteration shape checked against the host oracle (counts of records and mismatches).");
   m.def(
+      "pfsp_front_expand_probe",
+      [](int jobs, int machines, std::vector<int> p, int lb, U8 nodes, int best, int steps, int device) {
+        const PfspInstance in = make_instance(jobs, machines, std::move(p));
+        if (nodes.ndim() != 2) throw std::invalid_argument("nodes must be a (n, node_bytes) uint8 array");
+        const size_t nb = static_cast<size_t>(nodes.shape(1));
+        FrontExpandResult r;
+        {
+          py::gil_scoped_release nogil;
+          r = pfsp_front_expand_probe(in, lb, nodes.data(), static_cast<size_t>(nodes.shape(0)), best, steps, device);
+        }
+        if (nb == 0 || r.children.size() % nb) throw std::invalid_argument("nodes: not the front layout's node size");
+        py::array_t<uint8_t> c({static_cast<py::ssize_t>(r.children.size() / nb), static_cast<py::ssize_t>(nb)});
+        if (!r.children.empty()) std::memcpy(c.mutable_data(), r.children.data(), r.children.size());
+        py::dict d;
+        d["children"] = c;
+        d["counts"] = r.counts;
+        d["inner"] = r.inner;
+        d["bp"] = r.bp;
+        d["leaves"] = r.leaves;
+        d["best"] = r.best;
+        return d;
+      },
+      py::arg("jobs"), py::arg("machines"), py::arg("p"), py::arg("lb"), py::arg("nodes"), py::arg("best"),
+      py::arg("steps") = 0, py::arg("device") = 0,
+      "ONE front-kernel iteration over these (front-layout) parents, steps = 0: one level per kernel, steps >= 1: "
+      "local DFS of up to that many steps. Returns the nodes of each output chunk in order (children), the "
+      "per-chunk counts, the nodes each chunk pushed and expanded itself (inner), the window parents per chunk "
+      "(bp), the leaves counted and the incumbent after the launch.");
+  m.def(
       "pfsp_front_time",
       [](int jobs, int machines, std::vector<int> p, int lb, U8 nodes, int best, int device, size_t max_parents,
          int fuse_max, int deep_levels, int deep_per3, int deep_per4, int reps, int wide_levels, int local_min,

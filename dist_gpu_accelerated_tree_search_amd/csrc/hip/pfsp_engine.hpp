@@ -667,6 +667,112 @@ FrontProbeResult pfsp_front_probe_t(const PfspInstance& in, int lb, const void* 
   return res;
 }
 
+// Device allocations of a probe: freed on every exit path (a throwing HIP check included).
+struct ProbeAllocs {
+  std::vector<void*> owned;
+  ProbeAllocs() = default;
+  ProbeAllocs(const ProbeAllocs&) = delete;
+  ProbeAllocs& operator=(const ProbeAllocs&) = delete;
+  ~ProbeAllocs() {
+    for (void* d : owned) (void)hipFree(d);
+  }
+  // zeroed device memory
+  void* zeroed(size_t bytes) {
+    void* d = nullptr;
+    TTS_HIP_CHECK(hipMalloc(&d, std::max<size_t>(bytes, 16)));
+    owned.push_back(d);
+    TTS_HIP_CHECK(hipMemset(d, 0, std::max<size_t>(bytes, 16)));
+    return d;
+  }
+};
+
+// What ONE front-kernel iteration wrote (tests): the children of each output chunk in the
+// order the kernel laid them out, chunk after chunk. The bounds probe above checks what
+// the kernel evaluates, this one what it emits.
+//   steps == 0: one level per kernel — chunk c holds the survivors of parents
+//               [c * 256, (c + 1) * 256) in parent order, jobs ascending;
+//   steps >= 1: local DFS of up to `steps` steps — chunk c starts from parents
+//               [c * bp, (c + 1) * bp) and holds the stack it left (after one step: its
+//               parents' survivors, in the same order); inner[c] counts the nodes it
+//               pushed and expanded itself.
+struct FrontExpandResult {
+  std::vector<uint8_t> children;  // node bytes, chunks back to back
+  std::vector<int> counts;        // nodes per chunk
+  std::vector<int> inner;         // per chunk: pushed - left on the stack (local DFS)
+  int bp = 0;                     // window parents per chunk
+  unsigned long long leaves = 0;
+  int best = 0;
+};
+template <int M, int NJ = 20>
+FrontExpandResult pfsp_front_expand_probe_t(const PfspInstance& in, const void* nodes, size_t n, int best, int steps,
+                                            int device) {
+  using G = dev::FrontGeom<M, NJ>;
+  using Node = PfspFrontNode<M, NJ>;
+  if (steps < 0 || steps > G::LT) throw std::invalid_argument("front expand probe: 0 (one level) to LT local steps");
+  TTS_HIP_CHECK(hipSetDevice(device));
+  FrontExpandResult res;
+  res.best = best;
+  if (n == 0) return res;
+  const size_t nchunks = (n + G::BP - 1) / G::BP;
+  if (nchunks > static_cast<size_t>(G::MAXCHUNKS)) throw std::invalid_argument("front expand probe: too many parents");
+  dev::PfspFrontArgs<M, NJ> a{};
+  const std::vector<uint16_t> ptab = pfsp_front_fill_args(in, a);
+  ProbeAllocs mem;
+  uint16_t* dptab = static_cast<uint16_t*>(mem.zeroed(ptab.size() * sizeof(uint16_t)));
+  TTS_HIP_CHECK(hipMemcpy(dptab, ptab.data(), ptab.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
+  a.ptab = dptab;
+  size_t cap = 1;
+  while (cap < n) cap *= 2;
+  auto& pa = a.pool;
+  pa.ring = static_cast<Node*>(mem.zeroed(cap * sizeof(Node)));
+  TTS_HIP_CHECK(hipMemcpy(pa.ring, nodes, n * sizeof(Node), hipMemcpyHostToDevice));
+  for (int b = 0; b < 2; ++b) {
+    pa.buf[b] = static_cast<Node*>(mem.zeroed(nchunks * G::SLOT * sizeof(Node)));
+    pa.cnt[b] = static_cast<int*>(mem.zeroed(nchunks * sizeof(int)));
+    pa.lcnt[b] = static_cast<int*>(mem.zeroed(nchunks * sizeof(int)));
+  }
+  dev::PoolCtl h{};
+  h.slot[0].stack = n;
+  h.best.v = best;
+  h.best0 = best;
+  pa.ctl = static_cast<dev::PoolCtl*>(mem.zeroed(sizeof(dev::PoolCtl)));
+  TTS_HIP_CHECK(hipMemcpy(pa.ctl, &h, sizeof(h), hipMemcpyHostToDevice));
+  pa.cap_mask = cap - 1;
+  pa.max_parents = static_cast<int>(nchunks * G::BP);
+  pa.max_chunks = static_cast<int>(nchunks);
+  // the requested shape only: no fused / wide multi-level chunks, no dynamic DFS; a local
+  // window whatever the pool holds (the forced form of local_steps: a single step too)
+  pa.local_steps = -steps;
+  pa.local_min = 1;
+  const unsigned grid = static_cast<unsigned>(nchunks);
+  hipLaunchKernelGGL((dev::pfsp_front_kernel<M, NJ>), dim3(grid), dim3(dev::kBlock), 0, 0, a, 0);
+  TTS_HIP_CHECK(hipGetLastError());
+  TTS_HIP_CHECK(hipDeviceSynchronize());
+  // the chunks the iteration dealt: one per 256 parents, or the window spread over the grid
+  res.bp = steps == 0 ? G::BP : static_cast<int>(std::min<size_t>(G::BP, (n + grid - 1) / grid));
+  const size_t nout = (n + res.bp - 1) / res.bp;
+  if (nout > nchunks) throw std::runtime_error("front expand probe: more chunks than workgroups");
+  std::vector<int> lcnt(nout);
+  res.counts.assign(nout, 0);
+  res.inner.assign(nout, 0);
+  TTS_HIP_CHECK(hipMemcpy(res.counts.data(), pa.cnt[1], nout * sizeof(int), hipMemcpyDeviceToHost));
+  TTS_HIP_CHECK(hipMemcpy(lcnt.data(), pa.lcnt[1], nout * sizeof(int), hipMemcpyDeviceToHost));
+  for (size_t c = 0; c < nout; ++c) {
+    if (res.counts[c] < 0 || res.counts[c] > G::SLOT) throw std::runtime_error("front expand probe: chunk count out of range");
+    const size_t at = res.children.size(), bytes = static_cast<size_t>(res.counts[c]) * sizeof(Node);
+    res.children.resize(at + bytes);
+    if (bytes)
+      TTS_HIP_CHECK(hipMemcpy(res.children.data() + at, pa.buf[1] + c * G::SLOT, bytes, hipMemcpyDeviceToHost));
+    // (the per-chunk leaf word: leaves in the low half, inner nodes in the high half)
+    res.leaves += static_cast<uint32_t>(lcnt[c]) & 0xffffu;
+    res.inner[c] = static_cast<int>(static_cast<uint32_t>(lcnt[c]) >> 16);
+  }
+  TTS_HIP_CHECK(hipMemcpy(&h, pa.ctl, sizeof(h), hipMemcpyDeviceToHost));
+  if (h.overflow) throw std::runtime_error("front expand probe: the iteration reported an overflow");
+  res.best = h.best.v;
+  return res;
+}
+
 // Timing probe of ONE front-kernel iteration over a given window (the nodes loaded as
 // the pool), on the engine's grid: `reps` launches from the same state (min / median
 // ms), then one launch with the per-workgroup phase stamps (front_stamp). Returns
@@ -863,6 +969,10 @@ FrontProbeResult pfsp_front_probe_nj50(const PfspInstance& in, int lb, const voi
                                        size_t split_min);
 std::vector<double> pfsp_front_time_nj50(const PfspInstance& in, int lb, const void* nodes, size_t n, int best,
                                          const EngineConfig& cfg, int reps);
+FrontExpandResult pfsp_front_expand_probe(const PfspInstance& in, int lb, const void* nodes, size_t n, int best, int steps,
+                                          int device);
+FrontExpandResult pfsp_front_expand_probe_nj50(const PfspInstance& in, const void* nodes, size_t n, int best, int steps,
+                                               int device);
 
 #define TTS_PFSP_DECLARE_BUCKET(NJ)                                                                   \
   std::unique_ptr<IEngine> make_pfsp_engine_nj##NJ(const PfspInstance& in, int lb, const EngineConfig& cfg); \

@@ -21,4 +21,10 @@ std::vector<double> pfsp_front_time_nj50(const PfspInstance& in, int lb, const v
     return pfsp_front_time_t<decltype(mm)::value, 50>(in, lb, nodes, n, best, cfg, reps);
   });
 }
+FrontExpandResult pfsp_front_expand_probe_nj50(const PfspInstance& in, const void* nodes, size_t n, int best, int steps,
+                                               int device) {
+  return with_machine_bucket(in.machines, [&](auto mm) {
+    return pfsp_front_expand_probe_t<decltype(mm)::value, 50>(in, nodes, n, best, steps, device);
+  });
+}
 }  // namespace tts

@@ -29,6 +29,10 @@
 namespace tts {
 namespace dev {
 
+#ifndef TTS_EMIT_BALANCED_MAXM
+#define TTS_EMIT_BALANCED_MAXM 10  // machine buckets up to this one emit wave-balanced (FrontGeom::BAL)
+#endif
+
 template <int M, int NJ_ = 20>
 struct FrontGeom {
   static constexpr int NJ = NJ_;                        // children per parent at most (job bucket 20 or 50)
@@ -74,6 +78,13 @@ struct FrontGeom {
   // u16 row stride of the LDS p table (as PfspConsts::MS): 16 B for M <= 8, else 48 B
   static constexpr int MS = M <= 8 ? 8 : 24;
   static constexpr int RV = (M + 7) / 8;                // 16-B vectors holding one row's M values
+  // wave-balanced emit (front_emit_balanced): survivor descriptors a wave lists at a time.
+  // Up to 10 machines; 20 machines keep the per-lane loop: the fetched parent copy (22
+  // words) takes pfsp_front_kernel<20, 20> from 93 to 105 VGPRs, 5 to 4 waves per SIMD
+  // (profiles/r7/kernel_resources.md), and ta021 did not move (9.43 against 9.49 s, inside
+  // the spread: profiles/r7/full_and_regress.txt; A/B builds: -DTTS_EMIT_BALANCED_MAXM=20)
+  static constexpr int DW = 256;
+  static constexpr bool BAL = M <= TTS_EMIT_BALANCED_MAXM;
 };
 
 template <int M, int NJ = 20>
@@ -145,6 +156,9 @@ struct FrontSmem {
     };
   };
   PoolSmem<G::MAXCHUNKS> pool;
+  // wave-balanced emit: each wave's survivor descriptors, owner lane << 8 | job
+  // (front_emit_balanced; a wave touches its own row only)
+  uint16_t desc[kBlock / kWave][G::BAL ? G::DW : 1];
 };
 
 template <int M, int NJ>
@@ -409,6 +423,76 @@ __device__ inline void front_emit(const FrontSmem<M, NJ>& sm, const uint32_t (&w
   }
 }
 
+// Wave-balanced emit: the survivors of a wave's 64 parents, one per lane and round,
+// instead of each lane running its own survivors in turn (a wave then runs as many
+// chains as its luckiest lane has survivors: 2.6 - 7.7 on ta014's wide levels against
+// 1.1 - 2.8 rounds of 64, scripts/emit_imbalance.py). Output positions are those of the
+// per-lane loop: the k-th survivor (ascending job) of a lane whose exclusive scan offset
+// is off goes to store(off + k, child words, child remain).
+//   1. every lane lists its survivors as descriptors (owner lane << 8 | job) in its
+//      wave's LDS row, at its wave-local offset (off minus lane 0's): a short divergent
+//      walk, no chain;
+//   2. round r: lane i takes descriptor 64 r + i, fetches the owner's node words (and
+//      its packed remain when REM) across lanes, and builds and stores that child.
+// A wave with more than DW survivors (near the root under a loose incumbent) goes
+// through its list in windows of DW. Every lane of the wave must call this (nsurv = 0,
+// surv = 0 for a lane without a parent): ds_bpermute reads 0 from an inactive lane, so
+// the fetches run with all lanes active on clamped descriptors and only the chain and
+// the store are predicated. No workgroup barrier: waves share nothing here.
+template <int M, int NJ, bool REM, class Store>
+__device__ inline void front_emit_balanced(FrontSmem<M, NJ>& sm, const uint32_t (&w)[FrontGeom<M, NJ>::NW],
+                                           const uint32_t (&rp)[FrontGeom<M, NJ>::HW],
+                                           typename FrontGeom<M, NJ>::Mask surv, int off, int nsurv, Store store) {
+  using G = FrontGeom<M, NJ>;
+  constexpr int NW = G::NW, HW = G::HW, FO = G::FO, MO = G::MO, DW = G::DW;
+  const int lane = static_cast<int>(threadIdx.x) & (kWave - 1);
+  uint16_t* const desc = sm.desc[threadIdx.x / kWave];
+  const int base = __builtin_amdgcn_readfirstlane(off);
+  const int S = __builtin_amdgcn_readlane(off + nsurv, kWave - 1) - base;  // the wave's survivors
+  int pos = off - base;
+  static_assert((DW & (DW - 1)) == 0 && DW % kWave == 0, "a window is a power of two of whole rounds");
+  for (int s0 = 0; s0 < S; s0 += kWave) {
+    if ((s0 & (DW - 1)) == 0) {
+      // the next window of the list (the previous one's reads come first)
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+      __builtin_amdgcn_wave_barrier();
+      for (; surv && pos < s0 + DW; ++pos) {
+        desc[pos & (DW - 1)] = static_cast<uint16_t>((lane << 8) | mask_ctz(surv));
+        surv &= surv - 1;
+      }
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+      __builtin_amdgcn_wave_barrier();
+      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    }
+    const int s = s0 + lane;
+    const uint32_t d = desc[min(s, S - 1) & (DW - 1)];
+    const int j = static_cast<int>(d & 0xffu);
+    const int src4 = static_cast<int>(d >> 8) << 2;
+    uint32_t pw[NW], pr[HW];
+#pragma unroll
+    for (int i = 0; i < NW; ++i) {
+      const bool used = i == 0 || (i >= MO && i < FO + HW);
+      pw[i] = used ? static_cast<uint32_t>(__builtin_amdgcn_ds_bpermute(src4, static_cast<int>(w[i]))) : 0u;
+    }
+#pragma unroll
+    for (int h = 0; h < HW; ++h)
+      pr[h] = REM ? static_cast<uint32_t>(__builtin_amdgcn_ds_bpermute(src4, static_cast<int>(rp[h]))) : 0u;
+    if (s < S) {
+      uint32_t c[NW], cr[HW];
+      front_child<M, NJ>(sm, pw, j, c);
+      if constexpr (REM) {
+        const uint32_t* row = reinterpret_cast<const uint32_t*>(sm.ptab[j]);
+#pragma unroll
+        for (int h = 0; h < HW; ++h) cr[h] = pr[h] - row[h];  // the child's remain
+      } else {
+#pragma unroll
+        for (int h = 0; h < HW; ++h) cr[h] = 0;
+      }
+      store(base + s, c, cr);
+    }
+  }
+}
+
 // Position of the k-th (0-based) set bit of x, k < popcount(x): a 5-step binary
 // search on popcounts of the low halves (no loop over the bits).
 __device__ inline int kth_bit(uint32_t x, int k) {
@@ -569,6 +653,8 @@ __device__ inline int front_expand_tp_regs(const PfspFrontArgs<M, NJ>& a, FrontS
   }
   int tot = 0;
   int idx = block_exclusive_scan(nsurv, sm.scan, &tot);
+  // (the per-lane loop stays here: the balanced emit in this path too put the 10-machine
+  // kernel over its 80 registers, 16 B of scratch: profiles/r7/kernel_resources.md)
   while (surv) {
     const int j = mask_ctz(surv);
     surv &= surv - 1;
@@ -830,17 +916,30 @@ __device__ inline void front_local(const PfspFrontArgs<M, NJ>& a, FrontSmem<M, N
       const int lo = tot - nst;
       uint4* const dst = reinterpret_cast<uint4*>(stk + top);
       // (the scan's barrier: every thread holds its popped node in registers by now)
-      front_emit_to<M, NJ>(sm, w, surv, [&](int i, const uint32_t (&c)[G::NW], int j) {
-        const int o = off + i;
-        if (o >= lo) {
-          front_store<M, NJ>(&sm.stage[o - lo][0], c);
-          const uint32_t* row = reinterpret_cast<const uint32_t*>(sm.ptab[j]);
+      if constexpr (G::BAL) {
+        front_emit_balanced<M, NJ, true>(
+            sm, w, rp, surv, off, nsurv, [&](int o, const uint32_t (&c)[G::NW], const uint32_t (&cr)[G::HW]) {
+              if (o >= lo) {
+                front_store<M, NJ>(&sm.stage[o - lo][0], c);
 #pragma unroll
-          for (int h = 0; h < G::HW; ++h) sm.stage_r[o - lo][h] = rp[h] - row[h];  // the child's remain
-        } else {
-          front_store<M, NJ>(dst + o * G::VPN, c);
-        }
-      });
+                for (int h = 0; h < G::HW; ++h) sm.stage_r[o - lo][h] = cr[h];  // the child's remain
+              } else {
+                front_store<M, NJ>(dst + o * G::VPN, c);
+              }
+            });
+      } else {
+        front_emit_to<M, NJ>(sm, w, surv, [&](int i, const uint32_t (&c)[G::NW], int j) {
+          const int o = off + i;
+          if (o >= lo) {
+            front_store<M, NJ>(&sm.stage[o - lo][0], c);
+            const uint32_t* row = reinterpret_cast<const uint32_t*>(sm.ptab[j]);
+#pragma unroll
+            for (int h = 0; h < G::HW; ++h) sm.stage_r[o - lo][h] = rp[h] - row[h];  // the child's remain
+          } else {
+            front_store<M, NJ>(dst + o * G::VPN, c);
+          }
+        });
+      }
       top = tnew;
       pushed += tot;
       // pushes visible to the next step's pops (workgroup scope), and room left for
@@ -1363,7 +1462,16 @@ void pfsp_front_kernel(PfspFrontArgs<M, NJ> a, int t) {
       lcnt_out[ch] = (tot >> 13) & 0x1ff;
     }
     if (first) front_stamp(a, 5);
-    front_emit<M, NJ>(sm, w, surv, reinterpret_cast<uint4*>(bout + static_cast<size_t>(ch) * G::SLOT + off));
+    if constexpr (!G::BAL) {
+      front_emit<M, NJ>(sm, w, surv, reinterpret_cast<uint4*>(bout + static_cast<size_t>(ch) * G::SLOT + off));
+    } else {
+      uint4* const dst = reinterpret_cast<uint4*>(bout + static_cast<size_t>(ch) * G::SLOT);
+      const uint32_t norem[G::HW] = {};  // (children carry no remain here)
+      front_emit_balanced<M, NJ, false>(sm, w, norem, surv, off, nsurv,
+                                        [&](int o, const uint32_t (&c)[G::NW], const uint32_t (&)[G::HW]) {
+                                          front_store<M, NJ>(dst + o * G::VPN, c);
+                                        });
+    }
     if (first) front_stamp(a, 6);
   }
   front_stamp(a, 15);

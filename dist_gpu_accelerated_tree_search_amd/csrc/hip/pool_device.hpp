@@ -116,7 +116,9 @@ struct PoolArgs {
   int max_parents;
   int max_chunks;
   int fuse_max;     // two-level iterations for windows of at most this many parents (0: off)
-  int local_steps;  // > 1: local DFS iterations of up to this many steps per chunk (kernels that have them)
+  // > 1: local DFS iterations of up to this many steps per chunk (kernels that have them);
+  // < 0 (probes): local DFS of up to -local_steps steps, a single step included
+  int local_steps;
   int local_min;    // wide local DFS when the pool holds at least this many parents (0: 4 grid windows)
   int local_stride;    // local DFS chunks take strided window parents (ch, ch + nchunks, ...)
   int local_wide_steps;  // > 0: steps of a strided local window of at least 160 parents per workgroup
@@ -358,8 +360,8 @@ __device__ inline IterView pool_begin(const PoolArgs<Node>& pa, int t, int BP, P
   const u64 lmin = pa.local_min > 0 ? static_cast<u64>(pa.local_min) : 4 * full;
   // (an explicit pa.local_min may be below one grid window: wide BFS levels of a small
   // tree then also take a few local steps per dependent kernel)
-  v.local = LT > 1 && pa.local_steps > 1 && !armed && v.S + v.C >= (pa.local_min > 0 ? lmin : max(lmin, full));
-  v.steps = pa.local_steps;
+  v.local = LT > 1 && static_cast<unsigned>(pa.local_steps) > 1u && !armed && v.S + v.C >= (pa.local_min > 0 ? lmin : max(lmin, full));
+  v.steps = abs(pa.local_steps);
   // strided local windows below a backlog of four grid windows (a tree's wide levels); on a
   // backlog (ta021 LB1_d: millions of pooled nodes) contiguous dealing was faster
   v.stride = v.local && pa.local_stride && v.S + v.C < 4 * full;
