@@ -134,6 +134,8 @@ PYBIND11_MODULE(_tts_cpu, m) {
     return with_pfsp_problem(in, lb, [](auto prob) { return sizeof(typename decltype(prob)::Node); });
   });
   m.def("pfsp_front_layout", [](const PfspInstance& in, int lb) { return pfsp_front_ok(in, lb); });
+  m.def("pfsp_fronts_fit_u16", &pfsp_fronts_fit_u16,
+        "Every prefix completion time fits 16 bits (the GPU LB2 kernels' condition; sufficient, not necessary).");
   m.def(
       "pfsp_root",
       [](const PfspInstance& in, int lb) {

@@ -77,6 +77,22 @@ inline bool pfsp_front_ok(const PfspInstance& in, int lb) {
   return tot < 65536;
 }
 
+// Every prefix completion time of the instance fits 16 bits: the condition of the
+// permutation-node kernels that pack a front into a u16 (the `front | remain << 16` LDS
+// words of the LB2 kernels and their u16 child fronts, csrc/hip/pfsp_kernels.hpp).
+// A completion time is the length of a monotone staircase path through the machine x job
+// grid, not a column sum: it visits at most jobs + machines - 1 cells, so
+// (jobs + machines - 1) * max p bounds it, and so does the sum of all processing times.
+// Sufficient, not necessary (the longest path over all job orders is not computed).
+inline bool pfsp_fronts_fit_u16(const PfspInstance& in) {
+  long pmax = 0, tot = 0;
+  for (int v : in.p) {
+    pmax = std::max<long>(pmax, v);
+    tot += v;
+  }
+  return std::min((in.jobs + in.machines - 1) * pmax, tot) < 65536;
+}
+
 // job bucket of the front layout: 20 (32-bit job sets) or 50 (64-bit)
 inline int pfsp_front_jobs(int jobs) { return jobs <= 20 ? 20 : 50; }
 

@@ -157,11 +157,23 @@ inline int lb2_stride_wanted() {
 // machines are unchanged (a zero machine after the last one completes with it), and
 // LB2 walks only the instance's own pairs (npairs), so the bounds equal the host
 // oracle's for the real instance.
+//
+// Accepted values: every processing time, machine column sum (the remain half of the
+// LDS words), LB2 lag and tail must fit 16 bits. `u16_fronts` is set by the callers whose
+// kernels also keep prefix completion times in 16 bits (the LB2 kernels: the front half
+// of `front | remain << 16`, the u16 child fronts); those take only instances with
+// pfsp_fronts_fit_u16. The LB1 / LB1_d kernels hold fronts in 32-bit registers
+// (pfsp_lb1_parent) and need the table checks alone.
 template <int NJ, int M>
-inline PfspTableImages pfsp_fill_args(const PfspInstance& in, dev::PfspArgs<NJ, M>& a, bool pair_order = false) {
+inline PfspTableImages pfsp_fill_args(const PfspInstance& in, dev::PfspArgs<NJ, M>& a, bool pair_order,
+                                      bool u16_fronts) {
   using C = dev::PfspConsts<M>;
   if (in.machines > M || in.machines < 1) throw std::invalid_argument("machine count exceeds kernel instantiation");
   if (in.jobs > NJ) throw std::invalid_argument("job count exceeds kernel bucket");
+  for (int v : in.p)
+    if (v < 0 || v > 0xffff) throw std::invalid_argument("processing time does not fit 16 bits");
+  if (u16_fronts && !pfsp_fronts_fit_u16(in))
+    throw std::invalid_argument("instance too large for 16-bit fronts: (jobs + machines - 1) * max p >= 65536");
   const int MR = in.machines;
   const int PR = MR * (MR - 1) / 2;
   PfspTableImages img;
@@ -260,7 +272,7 @@ template <int NJ, int M, int LBK>
 std::unique_ptr<IEngine> make_pfsp_engine_t(const PfspInstance& in, const EngineConfig& cfg) {
   TTS_HIP_CHECK(hipSetDevice(cfg.device));
   dev::PfspArgs<NJ, M> a{};
-  const PfspTableImages img = pfsp_fill_args(in, a, LBK >= 2);
+  const PfspTableImages img = pfsp_fill_args(in, a, LBK >= 2, LBK >= 2);
   a.ptab = upload_vec(img.ptab);
   a.recs = upload_vec(img.recs);
   a.pinfo = upload_vec(img.pinfo);
@@ -285,7 +297,7 @@ std::vector<int> pfsp_gpu_bounds_t(const PfspInstance& in, const void* parents, 
   using Node = PfspNode<NJ>;
   TTS_HIP_CHECK(hipSetDevice(device));
   dev::PfspArgs<NJ, M> a{};
-  const PfspTableImages img = pfsp_fill_args(in, a);
+  const PfspTableImages img = pfsp_fill_args(in, a, false, LBK == 2);
   const Node* ph = static_cast<const Node*>(parents);
   std::vector<int> offsets(n + 1, 0);
   for (size_t i = 0; i < n; ++i) offsets[i + 1] = offsets[i] + (in.jobs - ph[i].depth);
@@ -356,7 +368,7 @@ std::vector<int> pfsp_expand_probe_t(const PfspInstance& in, const void* parents
     const size_t nchunks = (n + G::BP - 1) / G::BP;
     if (nchunks > static_cast<size_t>(G::MAXCHUNKS)) throw std::invalid_argument("expand probe: too many parents");
     dev::PfspArgs<NJ, M> a{};
-    const PfspTableImages img = pfsp_fill_args(in, a, true);
+    const PfspTableImages img = pfsp_fill_args(in, a, true, true);
     std::vector<void*> owned;
     auto up = [&](const auto& v) {
       auto* d = upload_vec(v);
@@ -514,7 +526,7 @@ ExpandProbeResult pfsp_lb1_expand_probe_t(const PfspInstance& in, const void* pa
   const size_t nchunks = (n + G::BP - 1) / G::BP;
   if (nchunks > static_cast<size_t>(G::MAXCHUNKS)) throw std::invalid_argument("lb1 expand probe: too many parents");
   dev::PfspArgs<NJ, M> a{};
-  const PfspTableImages img = pfsp_fill_args(in, a);
+  const PfspTableImages img = pfsp_fill_args(in, a, false, false);
   std::vector<void*> owned;
   auto up = [&](const auto& v) {
     auto* d = upload_vec(v);

@@ -79,3 +79,62 @@ def synthetic(jobs_: int, machines_: int, seed: int) -> np.ndarray:
     """Taillard-shaped synthetic instance (same LCG, chosen seed and shape)."""
     vals, _ = _lcg(max(1, seed), jobs_ * machines_)
     return vals.reshape(machines_, jobs_).astype(np.int32)
+
+
+# ---- instances at the top of the kernels' 16-bit value range (tests, docs/KNOBS.md) ----
+# All are functions of synthetic() alone, so they are the same everywhere.
+
+U16_MAX = 65535
+
+
+def scaled(jobs_: int, machines_: int, seed: int, k: int) -> np.ndarray:
+    """k * synthetic(...): every bound, front and makespan scales by k, and the tree of a
+    search that starts from k times the unscaled incumbent is the unscaled tree."""
+    if k < 1:
+        raise ValueError("k must be at least 1")
+    return (k * synthetic(jobs_, machines_, seed)).astype(np.int32)
+
+
+def _near(jobs_: int, machines_: int, seed: int, c: int) -> np.ndarray:
+    if c < 100:
+        raise ValueError("shape too large: the cell ceiling is below 100")
+    p = (c - 99) + synthetic(jobs_, machines_, seed)
+    p[0, 0] = c
+    return p.astype(np.int32)
+
+
+def near_limit(jobs_: int, machines_: int, seed: int) -> np.ndarray:
+    """Processing times of c-98..c with c = 65535 // (jobs + machines - 1), one cell at c:
+    the largest times at which every staircase path through the matrix (a prefix
+    completion time, an LB2 walk value) still fits 16 bits by the cell-count argument."""
+    return _near(jobs_, machines_, seed, U16_MAX // (jobs_ + machines_ - 1))
+
+
+def over_limit(jobs_: int, machines_: int, seed: int) -> np.ndarray:
+    """As near_limit with c = 65535 // jobs: every machine's column sum, every lag and
+    every tail fit 16 bits, the prefix completion times do not."""
+    return _near(jobs_, machines_, seed, U16_MAX // jobs_)
+
+
+def bottleneck(jobs_: int, machines_: int, b: int, seed: int, total: int = U16_MAX, q: int | None = None) -> np.ndarray:
+    """synthetic() rows with machine b's row multiplied by the largest integer that keeps
+    the sum of all processing times at or below `total`, then one cell of that row raised
+    so the sum is exactly `total`. With `q` the other rows are first reduced to
+    1 + (p - 1) % q (times of 1..q), which leaves more of the total to machine b."""
+    if not 0 <= b < machines_:
+        raise ValueError("b must be a machine index")
+    p = synthetic(jobs_, machines_, seed).astype(np.int64)
+    if q is not None:
+        if q < 1:
+            raise ValueError("q must be at least 1")
+        keep = p[b].copy()
+        p = 1 + (p - 1) % q
+        p[b] = keep
+    others = int(p.sum() - p[b].sum())
+    k = (total - others) // int(p[b].sum())
+    if k < 1:
+        raise ValueError("total too small for this shape")
+    p[b] *= k
+    p[b, 0] += total - int(p.sum())
+    assert int(p.sum()) == total
+    return p.astype(np.int32)
