@@ -9,6 +9,7 @@
 #include "../core/drivers_cpu.hpp"
 #include "../core/estimate.hpp"
 #include "../core/pfsp_front.hpp"
+#include "../core/pool_window.hpp"
 #include "../core/shm_control.hpp"
 #include "engine_binding.hpp"
 
@@ -134,6 +135,21 @@ PYBIND11_MODULE(_tts_cpu, m) {
     return with_pfsp_problem(in, lb, [](auto prob) { return sizeof(typename decltype(prob)::Node); });
   });
   m.def("pfsp_front_layout", [](const PfspInstance& in, int lb) { return pfsp_front_ok(in, lb); });
+  m.def(
+      "pool_deal",
+      [](uint64_t B, uint64_t spread, uint64_t cap, bool wide) {
+        if (spread == 0 || cap == 0) throw std::invalid_argument("pool_deal: spread and cap must be positive");
+        if (!wide && (B > kPoolWindowMax || spread > 0xffffffffull || cap > 0xffffffffull))
+          throw std::invalid_argument("pool_deal: the 32-bit form takes a window of at most 2^31 - 1 parents");
+        const PoolDeal d = wide ? pool_deal64(B, spread, cap)
+                                : pool_deal32(static_cast<uint32_t>(B), static_cast<uint32_t>(spread),
+                                              static_cast<uint32_t>(cap));
+        return py::make_tuple(d.per, d.bp, d.nchunks);
+      },
+      py::arg("B"), py::arg("spread"), py::arg("cap"), py::arg("wide") = false,
+      "A pool iteration's window of B parents dealt over `spread` chunks of at most `cap` parents (pool_begin): "
+      "(parents per chunk of an even spread, parents per chunk, chunks). wide: the 64-bit form the kernels' 32-bit "
+      "arithmetic replaced (core/pool_window.hpp).");
   m.def("pfsp_fronts_fit_u16", &pfsp_fronts_fit_u16,
         "Every prefix completion time fits 16 bits (the GPU LB2 kernels' condition; sufficient, not necessary).");
   m.def(

@@ -400,14 +400,16 @@ PYBIND11_MODULE(_tts_hip, m) {
       "bound of every iteration shape checked against the host oracle (counts of records and mismatches).");
   m.def(
       "pfsp_front_expand_probe",
-      [](int jobs, int machines, std::vector<int> p, int lb, U8 nodes, int best, int steps, int device) {
+      [](int jobs, int machines, std::vector<int> p, int lb, U8 nodes, int best, int steps, int device,
+         bool production) {
         const PfspInstance in = make_instance(jobs, machines, std::move(p));
         if (nodes.ndim() != 2) throw std::invalid_argument("nodes must be a (n, node_bytes) uint8 array");
         const size_t nb = static_cast<size_t>(nodes.shape(1));
         FrontExpandResult r;
         {
           py::gil_scoped_release nogil;
-          r = pfsp_front_expand_probe(in, lb, nodes.data(), static_cast<size_t>(nodes.shape(0)), best, steps, device);
+          r = pfsp_front_expand_probe(in, lb, nodes.data(), static_cast<size_t>(nodes.shape(0)), best, steps, device,
+                                      production);
         }
         if (nb == 0 || r.children.size() % nb) throw std::invalid_argument("nodes: not the front layout's node size");
         py::array_t<uint8_t> c({static_cast<py::ssize_t>(r.children.size() / nb), static_cast<py::ssize_t>(nb)});
@@ -422,11 +424,12 @@ PYBIND11_MODULE(_tts_hip, m) {
         return d;
       },
       py::arg("jobs"), py::arg("machines"), py::arg("p"), py::arg("lb"), py::arg("nodes"), py::arg("best"),
-      py::arg("steps") = 0, py::arg("device") = 0,
+      py::arg("steps") = 0, py::arg("device") = 0, py::arg("production") = false,
       "ONE front-kernel iteration over these (front-layout) parents, steps = 0: one level per kernel, steps >= 1: "
       "local DFS of up to that many steps. Returns the nodes of each output chunk in order (children), the "
       "per-chunk counts, the nodes each chunk pushed and expanded itself (inner), the window parents per chunk "
-      "(bp), the leaves counted and the incumbent after the launch.");
+      "(bp), the leaves counted and the incumbent after the launch. production: through the kernel's production "
+      "instantiation (no probe hooks, no dynamic local DFS) instead of the instrumented one.");
   m.def(
       "pfsp_front_time",
       [](int jobs, int machines, std::vector<int> p, int lb, U8 nodes, int best, int device, size_t max_parents,

@@ -75,6 +75,8 @@ class DeviceEngine final : public IEngine, public DeviceResource {
     const size_t bp = Traits::kParentsPerChunk;
     max_chunks_ = std::min<size_t>((cfg_.max_parents + bp - 1) / bp, Traits::kMaxChunks);
     cfg_.max_parents = max_chunks_ * bp;
+    // (the kernels deal the window in 32-bit arithmetic: core/pool_window.hpp)
+    if (cfg_.max_parents > kPoolWindowMax) throw std::invalid_argument("max_parents: the parent window must fit 31 bits");
     buf_nodes_ = max_chunks_ * static_cast<size_t>(Traits::kChildrenPerChunk);
     size_t cap = 1;
     while (cap * 2 * sizeof(Node) <= cfg_.ring_bytes) cap *= 2;

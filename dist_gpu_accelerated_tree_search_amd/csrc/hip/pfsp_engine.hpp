@@ -74,9 +74,20 @@ struct PfspFrontTraits {
   static constexpr int kLocalMin = 16384;
   static constexpr int kMaxChunks = G::MAXCHUNKS;
   static constexpr bool kDyn = true;  // dynamic local DFS iterations (front_dyn)
-  static void launch(const Args& a, int t, int grid, hipStream_t s) {
-    hipLaunchKernelGGL((dev::pfsp_front_kernel<M, NJ>), dim3(grid), dim3(dev::kBlock), 0, s, a, t);
+  // Does a launch with these arguments need the instrumented instantiation (the dynamic
+  // local DFS or a probe)? Everything else runs the production one.
+  static bool instrumented(const Args& a) { return a.pool.dyn || a.dbg_rec || a.dbg_blk; }
+  template <bool INSTR>
+  static void launch_t(const Args& a, int t, int grid, hipStream_t s) {
+    dev::FrontArgsT<M, NJ, INSTR> x;
+    static_cast<Args&>(x) = a;
+    hipLaunchKernelGGL((dev::pfsp_front_kernel<M, NJ, INSTR>), dim3(grid), dim3(dev::kBlock), 0, s, x, t);
   }
+  static void launch_as(bool instr, const Args& a, int t, int grid, hipStream_t s) {
+    if (instr) launch_t<true>(a, t, grid, s);
+    else launch_t<false>(a, t, grid, s);
+  }
+  static void launch(const Args& a, int t, int grid, hipStream_t s) { launch_as(instrumented(a), a, t, grid, s); }
   static void flatten(const dev::PoolArgs<Node>& pa, int b, int grid, hipStream_t s) {
     hipLaunchKernelGGL((dev::pool_flatten_kernel<Node, G::SLOT, G::MAXCHUNKS>), dim3(grid), dim3(dev::kBlock), 0, s,
                        pa, b);
@@ -85,10 +96,14 @@ struct PfspFrontTraits {
     hipLaunchKernelGGL((dev::pool_finalize_kernel<Node, G::MAXCHUNKS>), dim3(1), dim3(dev::kBlock), 0, s, pa, b, slot);
   }
   static int blocks_per_cu() {
-    int n = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, dev::pfsp_front_kernel<M, NJ>, dev::kBlock, 0) != hipSuccess)
+    // one grid serves both instantiations: what fits of either, capped as measured
+    int n = 0, np = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, dev::pfsp_front_kernel<M, NJ, true>, dev::kBlock, 0) !=
+            hipSuccess ||
+        hipOccupancyMaxActiveBlocksPerMultiprocessor(&np, dev::pfsp_front_kernel<M, NJ, false>, dev::kBlock, 0) !=
+            hipSuccess)
       return 1;
-    return std::min(n, G::GRID_WGS);  // FrontGeom::GRID_WGS (the API over-reports by one)
+    return std::min(std::min(n, np), G::GRID_WGS);  // FrontGeom::GRID_WGS (the API over-reports by one)
   }
 };
 
@@ -707,6 +722,8 @@ struct ProbeAllocs {
 //               [c * bp, (c + 1) * bp) and holds the stack it left (after one step: its
 //               parents' survivors, in the same order); inner[c] counts the nodes it
 //               pushed and expanded itself.
+// production: launch the production instantiation of the kernel (pfsp_front_kernel INSTR
+// false) instead of the instrumented one.
 struct FrontExpandResult {
   std::vector<uint8_t> children;  // node bytes, chunks back to back
   std::vector<int> counts;        // nodes per chunk
@@ -717,7 +734,7 @@ struct FrontExpandResult {
 };
 template <int M, int NJ = 20>
 FrontExpandResult pfsp_front_expand_probe_t(const PfspInstance& in, const void* nodes, size_t n, int best, int steps,
-                                            int device) {
+                                            int device, bool production = false) {
   using G = dev::FrontGeom<M, NJ>;
   using Node = PfspFrontNode<M, NJ>;
   if (steps < 0 || steps > G::LT) throw std::invalid_argument("front expand probe: 0 (one level) to LT local steps");
@@ -757,7 +774,9 @@ FrontExpandResult pfsp_front_expand_probe_t(const PfspInstance& in, const void* 
   pa.local_steps = -steps;
   pa.local_min = 1;
   const unsigned grid = static_cast<unsigned>(nchunks);
-  hipLaunchKernelGGL((dev::pfsp_front_kernel<M, NJ>), dim3(grid), dim3(dev::kBlock), 0, 0, a, 0);
+  // (the instrumented instantiation unless the production one is asked for: the launch
+  // sets no probe pointer, so the two must write the same bytes)
+  PfspFrontTraits<M, NJ>::launch_as(!production, a, 0, static_cast<int>(grid), 0);
   TTS_HIP_CHECK(hipGetLastError());
   TTS_HIP_CHECK(hipDeviceSynchronize());
   // the chunks the iteration dealt: one per 256 parents, or the window spread over the grid
@@ -866,7 +885,7 @@ std::vector<double> pfsp_front_time_t(const PfspInstance& in, int lb, const void
   for (int r = 0; r < std::max(1, reps); ++r) {
     restore();
     TTS_HIP_CHECK(hipEventRecord(e0, 0));
-    hipLaunchKernelGGL((dev::pfsp_front_kernel<M, NJ>), dim3(grid), dim3(dev::kBlock), 0, 0, a, 0);
+    PfspFrontTraits<M, NJ>::launch(a, 0, grid, 0);  // as an engine launches it (production unless dynamic)
     TTS_HIP_CHECK(hipGetLastError());
     TTS_HIP_CHECK(hipEventRecord(e1, 0));
     TTS_HIP_CHECK(hipEventSynchronize(e1));
@@ -879,7 +898,7 @@ std::vector<double> pfsp_front_time_t(const PfspInstance& in, int lb, const void
   std::sort(ms.begin(), ms.end());
   restore();
   a.dbg_blk = static_cast<unsigned long long*>(dalloc(static_cast<size_t>(grid) * 16 * sizeof(unsigned long long)));
-  hipLaunchKernelGGL((dev::pfsp_front_kernel<M, NJ>), dim3(grid), dim3(dev::kBlock), 0, 0, a, 0);
+  PfspFrontTraits<M, NJ>::launch(a, 0, grid, 0);  // (the stamps: the instrumented instantiation)
   TTS_HIP_CHECK(hipGetLastError());
   TTS_HIP_CHECK(hipDeviceSynchronize());
   std::vector<unsigned long long> blk(static_cast<size_t>(grid) * 16);
@@ -982,9 +1001,9 @@ FrontProbeResult pfsp_front_probe_nj50(const PfspInstance& in, int lb, const voi
 std::vector<double> pfsp_front_time_nj50(const PfspInstance& in, int lb, const void* nodes, size_t n, int best,
                                          const EngineConfig& cfg, int reps);
 FrontExpandResult pfsp_front_expand_probe(const PfspInstance& in, int lb, const void* nodes, size_t n, int best, int steps,
-                                          int device);
+                                          int device, bool production = false);
 FrontExpandResult pfsp_front_expand_probe_nj50(const PfspInstance& in, const void* nodes, size_t n, int best, int steps,
-                                               int device);
+                                               int device, bool production);
 
 #define TTS_PFSP_DECLARE_BUCKET(NJ)                                                                   \
   std::unique_ptr<IEngine> make_pfsp_engine_nj##NJ(const PfspInstance& in, int lb, const EngineConfig& cfg); \

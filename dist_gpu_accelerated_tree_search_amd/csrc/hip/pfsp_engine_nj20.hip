@@ -24,11 +24,11 @@ std::vector<double> pfsp_front_time(const PfspInstance& in, int lb, const void* 
   });
 }
 FrontExpandResult pfsp_front_expand_probe(const PfspInstance& in, int lb, const void* nodes, size_t n, int best, int steps,
-                                          int device) {
+                                          int device, bool production) {
   if (!pfsp_front_ok(in, lb)) throw std::invalid_argument("front expand probe: the front layout does not apply");
-  if (in.jobs > 20) return pfsp_front_expand_probe_nj50(in, nodes, n, best, steps, device);
+  if (in.jobs > 20) return pfsp_front_expand_probe_nj50(in, nodes, n, best, steps, device, production);
   return with_machine_bucket(in.machines, [&](auto mm) {
-    return pfsp_front_expand_probe_t<decltype(mm)::value>(in, nodes, n, best, steps, device);
+    return pfsp_front_expand_probe_t<decltype(mm)::value>(in, nodes, n, best, steps, device, production);
   });
 }
 

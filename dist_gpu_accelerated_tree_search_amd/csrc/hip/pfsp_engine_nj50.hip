@@ -22,9 +22,9 @@ std::vector<double> pfsp_front_time_nj50(const PfspInstance& in, int lb, const v
   });
 }
 FrontExpandResult pfsp_front_expand_probe_nj50(const PfspInstance& in, const void* nodes, size_t n, int best, int steps,
-                                               int device) {
+                                               int device, bool production) {
   return with_machine_bucket(in.machines, [&](auto mm) {
-    return pfsp_front_expand_probe_t<decltype(mm)::value, 50>(in, nodes, n, best, steps, device);
+    return pfsp_front_expand_probe_t<decltype(mm)::value, 50>(in, nodes, n, best, steps, device, production);
   });
 }
 }  // namespace tts

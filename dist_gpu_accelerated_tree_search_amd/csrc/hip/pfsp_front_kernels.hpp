@@ -109,14 +109,34 @@ struct PfspFrontArgs {
   // per-workgroup phase timeline (timing probe only, null in production): wall clock at
   // 16 stamps per workgroup (front_stamp)
   unsigned long long* dbg_blk;
+  static constexpr bool kInstr = true;  // the probe pointers are looked at (FrontArgsT)
 };
+
+// The arguments as a search kernel instantiation takes them: the same bytes, the type
+// saying whether the probe hooks exist (pfsp_front_kernel INSTR). The device functions
+// below take the arguments as `const A&` and ask front_rec / front_blk, which are
+// constant false for the production instantiation: its code holds no stamp and no record.
+template <int M, int NJ, bool INSTR>
+struct FrontArgsT : PfspFrontArgs<M, NJ> {
+  static constexpr bool kInstr = INSTR;
+};
+template <class A>
+__device__ inline bool front_rec(const A& a) {
+  if constexpr (A::kInstr) return a.dbg_rec != nullptr;
+  else return false;
+}
+template <class A>
+__device__ inline bool front_blk(const A& a) {
+  if constexpr (A::kInstr) return a.dbg_blk != nullptr;
+  else return false;
+}
 
 // Timing probe stamp k of this workgroup (thread 0; a.dbg_blk is null in production).
 // Stamp 0 also records where the workgroup runs (raw HW_ID: wave / SIMD / CU / SE fields,
 // and the XCC id) in words 12 / 13; front_local puts its node counts in word 14.
 template <class A>
 __device__ inline void front_stamp(const A& a, int k) {
-  if (a.dbg_blk && threadIdx.x == 0) {
+  if (front_blk(a) && threadIdx.x == 0) {
     a.dbg_blk[blockIdx.x * 16 + k] = wall_clock64();
     if (k == 0) {
       a.dbg_blk[blockIdx.x * 16 + 12] = __builtin_amdgcn_s_getreg((31 << 11) | 4);
@@ -345,26 +365,26 @@ __device__ inline void front_remain(const FrontSmem<M, NJ>& sm, const uint32_t (
 
 // Bounds of every child of the parent held in w: emit(j, lb) for each unscheduled job j.
 // (the parent's packed remain rp given)
-template <int M, int NJ, class Emit>
-__device__ inline void front_parent_r(const PfspFrontArgs<M, NJ>& a, const FrontSmem<M, NJ>& sm,
+template <int M, int NJ, class A, class Emit>
+__device__ inline void front_parent_r(const A& a, const FrontSmem<M, NJ>& sm,
                                       const uint32_t (&w)[FrontGeom<M, NJ>::NW], const uint32_t (&rp)[FrontGeom<M, NJ>::HW],
                                       Emit emit, int kind) {
   uint32_t fb[M], rb[M];
   front_broadcast<M, NJ>(a, w, rp, fb, rb);
   front_bounds_x2<M, NJ>(sm, fb, rb, front_mask<M, NJ>(w), [&](int j, int lb) {
-    if (a.dbg_rec) front_dbg<M, NJ>(a, kind, w, rp, j, lb);
+    if (front_rec(a)) front_dbg<M, NJ>(a, kind, w, rp, j, lb);
     emit(j, lb);
   });
 }
 
-template <int M, int NJ, class Emit>
-__device__ inline void front_parent(const PfspFrontArgs<M, NJ>& a, const FrontSmem<M, NJ>& sm,
+template <int M, int NJ, class A, class Emit>
+__device__ inline void front_parent(const A& a, const FrontSmem<M, NJ>& sm,
                                     const uint32_t (&w)[FrontGeom<M, NJ>::NW], Emit emit, int kind = kDbgOne) {
   uint32_t rp[FrontGeom<M, NJ>::HW], fb[M], rb[M];
   front_remain<M, NJ>(sm, w, rp);
   front_broadcast<M, NJ>(a, w, rp, fb, rb);
   front_bounds_x2<M, NJ>(sm, fb, rb, front_mask<M, NJ>(w), [&](int j, int lb) {
-    if (a.dbg_rec) front_dbg<M, NJ>(a, kind, w, rp, j, lb);
+    if (front_rec(a)) front_dbg<M, NJ>(a, kind, w, rp, j, lb);
     emit(j, lb);
   });
 }
@@ -545,8 +565,8 @@ struct FrontKeepAll {
 };
 
 // (T children, offsets in sm.coff: front_child_offsets)
-template <int M, int NJ, class Store, class Keep = FrontKeepAll>
-__device__ inline int front_expand_cp(const PfspFrontArgs<M, NJ>& a, FrontSmem<M, NJ>& sm, const uint4 (*src)[FrontGeom<M, NJ>::VPN],
+template <int M, int NJ, class A, class Store, class Keep = FrontKeepAll>
+__device__ inline int front_expand_cp(const A& a, FrontSmem<M, NJ>& sm, const uint4 (*src)[FrontGeom<M, NJ>::VPN],
                                       const uint32_t (*rem)[FrontGeom<M, NJ>::HW], int n, int T, int best, int& nleaf,
                                       Store store, Keep keep = {}, int kind = kDbgCp) {
   using G = FrontGeom<M, NJ>;
@@ -599,7 +619,7 @@ __device__ inline int front_expand_cp(const PfspFrontArgs<M, NJ>& a, FrontSmem<M
         lb = max(lb, sv + rm(m));
         tt = sv + pm(m);
       }
-      if (a.dbg_rec) front_dbg<M, NJ>(a, kind, w, rp, j, lb);
+      if (front_rec(a)) front_dbg<M, NJ>(a, kind, w, rp, j, lb);
       const bool kp = keep(lo, j);
       if (static_cast<int>(w[0] & 0xffu) + 1 == a.jobs) {
         nleaf += kp;
@@ -627,8 +647,8 @@ __device__ inline int front_expand_cp(const PfspFrontArgs<M, NJ>& a, FrontSmem<M
 // path: fewer instructions per child than front_expand_cp (no parent search, one node
 // load per parent), and the serial loop is short once most lanes hold a node.
 // (the node and its packed remain in registers; w = 0 for a thread without a node)
-template <int M, int NJ, class Store, class Keep = FrontKeepAll>
-__device__ inline int front_expand_tp_regs(const PfspFrontArgs<M, NJ>& a, FrontSmem<M, NJ>& sm,
+template <int M, int NJ, class A, class Store, class Keep = FrontKeepAll>
+__device__ inline int front_expand_tp_regs(const A& a, FrontSmem<M, NJ>& sm,
                                            const uint32_t (&w)[FrontGeom<M, NJ>::NW], const uint32_t (&rp)[FrontGeom<M, NJ>::HW],
                                            int best, int& nleaf, Store store, int kind = kDbgTp, Keep keep = {}) {
   using G = FrontGeom<M, NJ>;
@@ -640,7 +660,7 @@ __device__ inline int front_expand_tp_regs(const PfspFrontArgs<M, NJ>& a, FrontS
     uint32_t fb[M], rb[M];
     front_broadcast<M, NJ>(a, w, rp, fb, rb);
     front_bounds_x2<M, NJ>(sm, fb, rb, front_mask<M, NJ>(w), [&](int j, int lb) {
-      if (a.dbg_rec) front_dbg<M, NJ>(a, kind, w, rp, j, lb);
+      if (front_rec(a)) front_dbg<M, NJ>(a, kind, w, rp, j, lb);
       const bool kp = keep(static_cast<int>(threadIdx.x), j);
       if (leaf) {
         nleaf += kp;
@@ -668,8 +688,8 @@ __device__ inline int front_expand_tp_regs(const PfspFrontArgs<M, NJ>& a, FrontS
   return tot;
 }
 
-template <int M, int NJ, class Store, class Keep = FrontKeepAll>
-__device__ inline int front_expand_tp(const PfspFrontArgs<M, NJ>& a, FrontSmem<M, NJ>& sm,
+template <int M, int NJ, class A, class Store, class Keep = FrontKeepAll>
+__device__ inline int front_expand_tp(const A& a, FrontSmem<M, NJ>& sm,
                                       const uint4 (*src)[FrontGeom<M, NJ>::VPN], const uint32_t (*rem)[FrontGeom<M, NJ>::HW],
                                       int n, int best, int& nleaf, Store store, Keep keep = {}, int kind = kDbgTp) {
   using G = FrontGeom<M, NJ>;
@@ -704,8 +724,8 @@ __device__ inline int front_expand_tp(const PfspFrontArgs<M, NJ>& a, FrontSmem<M
 // nodes (high half of the leaf word); everything that goes out is the chunk's output.
 // One dependent kernel covers up to 4 tree levels of a narrow window (ref: one kernel
 // per level, pfsp_multigpu_cuda.c:221-332).
-template <int M, int NJ>
-__device__ inline void front_multi_level(const PfspFrontArgs<M, NJ>& a, FrontSmem<M, NJ>& sm, const IterView& v, int t,
+template <int M, int NJ, class A>
+__device__ inline void front_multi_level(const A& a, FrontSmem<M, NJ>& sm, const IterView& v, int t,
                                          int best) {
   using G = FrontGeom<M, NJ>;
   using Node = PfspFrontNode<M, NJ>;
@@ -832,8 +852,8 @@ __device__ inline void front_multi_level(const PfspFrontArgs<M, NJ>& a, FrontSme
 // (cnt); nodes pushed and expanded in between are explored tree nodes (high half of
 // the leaf word). Pops read slots [top - n, top) and pushes write from top - n on:
 // every pop is in registers before the scan's barrier that precedes the first push.
-template <int M, int NJ>
-__device__ inline void front_local(const PfspFrontArgs<M, NJ>& a, FrontSmem<M, NJ>& sm, const IterView& v, int t, int best) {
+template <int M, int NJ, class A>
+__device__ inline void front_local(const A& a, FrontSmem<M, NJ>& sm, const IterView& v, int t, int best) {
   using G = FrontGeom<M, NJ>;
   using Node = PfspFrontNode<M, NJ>;
   const int tid = threadIdx.x;
@@ -953,7 +973,7 @@ __device__ inline void front_local(const PfspFrontArgs<M, NJ>& a, FrontSmem<M, N
     if (tid == 0) {
       cnt_out[ch] = top;
       lcnt_out[ch] = leaves | ((pushed - top) << 16);
-      if (a.dbg_blk && ch == static_cast<int>(blockIdx.x))
+      if (front_blk(a) && ch == static_cast<int>(blockIdx.x))
         a.dbg_blk[blockIdx.x * 16 + 14] = static_cast<unsigned long long>(pushed - top) |
                                           (static_cast<unsigned long long>(top) << 32);
     }
@@ -1371,9 +1391,18 @@ __device__ inline void front_dyn(const PfspFrontArgs<M, NJ>& a, FrontSmem<M, NJ>
 // 4 for 20 (f, remain and a p row stay in registers without scratch); the engine's grid
 // holds FrontGeom::GRID_WGS workgroups per CU (5 of the 6 up to 10 machines). (Compiled for 7 — 94 SGPRs, 72 spilled to VGPR
 // lanes — the headline was 3 % slower than at 6.)
-template <int M, int NJ = 20>
+//
+// Two instantiations. The production one (INSTR false: every launch without a probe and
+// without the dynamic local DFS, picked on the host by PfspFrontTraits::launch) takes its
+// arguments as FrontArgsT<M, NJ, false>, whose probe queries are constant false, and passes
+// DYN false to pool_begin, so the stamps, the probe records and front_dyn with its polling
+// are not in its code: SGPR spills 123 -> 78 for <10, 20> and 110 -> 41 for <5, 20>, no
+// scratch, 88 scalar and 116 vector instructions fewer per wave over a ta014 solve, every
+// kernel of the solve 1.2 - 2.2 us shorter (profiles/r8/kernel_resources.md, pmc/,
+// timeline/). The instrumented one is the whole kernel.
+template <int M, int NJ = 20, bool INSTR = true>
 __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(FrontGeom<M, NJ>::WAVES)))
-void pfsp_front_kernel(PfspFrontArgs<M, NJ> a, int t) {
+void pfsp_front_kernel(FrontArgsT<M, NJ, INSTR> a, int t) {
   using G = FrontGeom<M, NJ>;
   using Node = PfspFrontNode<M, NJ>;
   __shared__ FrontSmem<M, NJ> sm;
@@ -1389,7 +1418,7 @@ void pfsp_front_kernel(PfspFrontArgs<M, NJ> a, int t) {
     ptv[i] = x < a.jobs * G::MS ? a.ptab[x] : 0;
   }
   const IterView v =
-      pool_begin<Node, G::MAXCHUNKS>(pa, t, G::BP, sm.pool, a.bpf, G::LT, G::NJ * (G::NJ - 1), G::LMAX, true);
+      pool_begin<Node, G::MAXCHUNKS>(pa, t, G::BP, sm.pool, a.bpf, G::LT, G::NJ * (G::NJ - 1), G::LMAX, INSTR);
   front_stamp(a, 1);
   if (v.B == 0 || v.overflow) return;
   {
@@ -1405,10 +1434,12 @@ void pfsp_front_kernel(PfspFrontArgs<M, NJ> a, int t) {
   pool_spill_leftovers<Node, G::SLOT, G::MAXCHUNKS>(pa, v, t, sm.pool);
   __syncthreads();
   front_stamp(a, 2);
-  if (v.dyn) {
-    front_dyn<M, NJ>(a, sm, v, t, best);
-    front_stamp(a, 15);
-    return;
+  if constexpr (INSTR) {
+    if (v.dyn) {
+      front_dyn<M, NJ>(a, sm, v, t, best);
+      front_stamp(a, 15);
+      return;
+    }
   }
   if (v.local) {
     front_local<M, NJ>(a, sm, v, t, best);

@@ -23,6 +23,7 @@
 
 #include <cstddef>
 
+#include "../core/pool_window.hpp"
 #include "device_common.hpp"
 
 namespace tts {
@@ -308,6 +309,9 @@ __device__ inline IterView pool_begin(const PoolArgs<Node>& pa, int t, int BP, P
   // per-chunk counts are read once nch is known: reading the whole window's
   // counts speculatively in the same round trip made ta014 slower (0.32 -> 0.39
   // ms, profiles/r1/r1q: cold count lines), though ta008 gained 4 %.
+  // (Requesting only the first min(grid, max_chunks) counts with the control line — what a
+  // local DFS iteration writes — and masking by nch afterwards was measured too: pool_begin
+  // +0.25 us per workgroup, ta014 +0.0015 ms, ta008 -1 %: profiles/r8/early_counts_ab.txt.)
   IterView v;
   v.S = ctl->slot[s_in].stack;
   v.nch_in = ctl->slot[s_in].nch;
@@ -397,7 +401,14 @@ __device__ inline IterView pool_begin(const PoolArgs<Node>& pa, int t, int BP, P
   const bool fuse_split = v.split && LMAX > 2 && GROW2 > 0;
   v.fused = !v.local && BPF > 0 && (!armed || fuse_armed || fuse_split) &&
             v.B <= static_cast<u64>(min(pa.fuse_max, BPF * pa.max_chunks));
+  // The dealing runs in 32-bit arithmetic (core/pool_window.hpp): the window is at most
+  // pa.max_parents, an int. Every wave of every workgroup does this before its first
+  // bound, and the four u64 divisions it replaces were most of pool_begin's scalar
+  // instructions (SALU instructions per wave before / after: profiles/r8/pmc/).
+  static_assert(sizeof(pa.max_parents) == sizeof(int), "the window (<= max_parents) must fit 32-bit arithmetic");
+  const uint32_t B32 = static_cast<uint32_t>(v.B);
   int bp = BP;
+  int nchunks = -1;  // (set with bp where a shape deals the window itself)
   v.levels = v.fused ? 2 : 1;
   if (v.fused) {
     // up to BPF parents per two-level chunk, fewer when the window is narrower than the
@@ -406,29 +417,36 @@ __device__ inline IterView pool_begin(const PoolArgs<Node>& pa, int t, int BP, P
     // same frontier by position): the window is then spread over a fixed 1024 chunks
     // instead of the grid (chunk order, not workgroup order, lays out the output). Never
     // more chunks than the count / slot arrays hold (max_chunks; the grid is within it).
-    const u64 spread = min(armed ? 1024ull : static_cast<u64>(gridDim.x), static_cast<u64>(pa.max_chunks));
-    const u64 per = (v.B + spread - 1) / spread;
-    bp = static_cast<int>(min(static_cast<u64>(BPF), max(per, 1ull)));
+    const uint32_t spread = min(armed ? 1024u : gridDim.x, static_cast<uint32_t>(pa.max_chunks));
+    const PoolDeal d = pool_deal32(B32, spread, static_cast<uint32_t>(BPF));
+    const uint32_t per = d.per;
+    bp = d.bp;
+    nchunks = d.nchunks;
     // narrower windows go deeper: 3 or 4 levels per dependent kernel while a chunk's
     // levels stay in LDS (never while armed: the split must see the replicated levels)
     const int lmax = min(LMAX, pa.deep_levels);
-    if (!armed && lmax >= 3 && per <= static_cast<u64>(pa.deep_per[0])) v.levels = 3;
-    if (!armed && lmax >= 4 && per <= static_cast<u64>(pa.deep_per[1])) v.levels = 4;
+    // (a negative limit compares as a huge one, as in the 64-bit form)
+    if (!armed && lmax >= 3 && per <= static_cast<uint32_t>(pa.deep_per[0])) v.levels = 3;
+    if (!armed && lmax >= 4 && per <= static_cast<uint32_t>(pa.deep_per[1])) v.levels = 4;
   } else if (LMAX > 2 && !v.local && !armed && pa.wide_levels >= 2 && v.B <= static_cast<u64>(pa.fuse_max) &&
-             (v.B + gridDim.x - 1) / gridDim.x <= static_cast<u64>(BP)) {
+             pool_ceil_div32(B32, gridDim.x) <= static_cast<uint32_t>(BP)) {
     // wide multi-level: every workgroup takes one chunk of up to one parent per thread
     // (the kernel's first level runs from the pool, the next ones from LDS)
     v.fused = true;
-    bp = static_cast<int>(max((v.B + gridDim.x - 1) / gridDim.x, 1ull));
+    const PoolDeal d = pool_deal32(B32, gridDim.x, static_cast<uint32_t>(BP));
+    bp = d.bp;
+    nchunks = d.nchunks;
     v.levels = min(pa.wide_levels, LMAX);
   }
   if (v.local) {
     // spread a window smaller than the grid over every workgroup
-    const u64 per = (v.B + gridDim.x - 1) / gridDim.x;
-    bp = static_cast<int>(min(static_cast<u64>(BP), max(per, 1ull)));
+    const PoolDeal d = pool_deal32(B32, gridDim.x, static_cast<uint32_t>(BP));
+    bp = d.bp;
+    nchunks = d.nchunks;
   }
+  if (nchunks < 0) nchunks = static_cast<int>(pool_ceil_div32(B32, static_cast<uint32_t>(BP)));
   v.bp = bp;
-  v.nchunks = v.dyn ? static_cast<int>(gridDim.x) : static_cast<int>((v.B + bp - 1) / bp);
+  v.nchunks = v.dyn ? static_cast<int>(gridDim.x) : nchunks;
   const bool overflow = v.overflow;
   v.overflow = overflow || bad_split;
   if (blockIdx.x == 0) {
