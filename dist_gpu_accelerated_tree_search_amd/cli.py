@@ -65,6 +65,9 @@ def _pfsp_parser(cls=argparse.ArgumentParser) -> argparse.ArgumentParser:
     ap.add_argument("--heuristic-ub", action="store_true",
                     help="-u 0: start from a heuristic incumbent (LB1 beam dive + NEH) instead of +inf; the "
                          "explored tree is then not the reference's -u 0 quantity (recorded as initial_ub)")
+    ap.add_argument("--front-wide", action="store_true",
+                    help="LB1 / LB1_d on 51-100 jobs: front-carrying nodes with 128-bit job sets instead of "
+                         "permutation nodes (sets TTS_FRONT_WIDE=1 for this process and every rank it spawns)")
     ap.add_argument("--json", default=None, help="append a JSON run record to this file")
     ap.add_argument("--csv-dir", default=".", help="directory of the CSV statistics files")
     ap.add_argument("--no-csv", action="store_true")
@@ -172,6 +175,9 @@ def pfsp_main(argv: list[str]) -> int:
     _validate_pfsp(a)
     if a.heuristic_ub:
         os.environ.setdefault("TTS_DIVE", "32")  # models.pfsp.PfspModel.search_best
+    if a.front_wide:
+        # before any model, engine or rank exists: csrc/core/pfsp_front.hpp pfsp_front_ok reads it
+        os.environ["TTS_FRONT_WIDE"] = "1"
     from .models.pfsp import EngineOptions, PfspModel
     from .search import solve_cpu, solve_engine
 
@@ -369,6 +375,14 @@ def main(argv: list[str] | None = None) -> int:
     if not argv or argv[0] not in ("pfsp", "nqueens"):
         sys.stderr.write(__doc__ or "")
         return 2
+    if argv[0] == "pfsp":
+        # --front-wide reaches the ranks through the environment, and they inherit the
+        # forkserver's: set it before that exists (pfsp_main sets it again for direct callers)
+        try:
+            if _pfsp_parser(_QuietParser).parse_args(argv[1:]).front_wide:
+                os.environ["TTS_FRONT_WIDE"] = "1"
+        except (ValueError, SystemExit):
+            pass
     if _spawn_planned(argv):
         # the rank processes come from a forkserver that must exist before this process
         # makes any HIP call (gpu_count, engines): a GPU-initialised process never forks

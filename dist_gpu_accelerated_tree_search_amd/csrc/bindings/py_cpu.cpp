@@ -201,9 +201,9 @@ PYBIND11_MODULE(_tts_cpu, m) {
           const Node* p = array_nodes<Node>(nodes, n);
           for (size_t i = 0; i < n; ++i) {
             if constexpr (is_front_problem<P>::value) {
-              int by_job[64];
+              int by_job[P::kMaxJ];
               prob.children_bounds(p[i], by_job);
-              for (auto x = p[i].rest; x; x &= x - 1) out.push_back(by_job[mask_ctz(x)]);
+              for (auto x = p[i].rest; !mask_empty(x); mask_pop_low(x)) out.push_back(by_job[mask_ctz(x)]);
             } else {
               throw std::invalid_argument("pfsp_children_bounds: front layout only");
             }

@@ -62,21 +62,6 @@ inline PfspPadded pfsp_padded_tables(const PfspInstance& in, int MB) {
   return t;
 }
 
-// The front layout applies: LB1 / LB1_d, at most 50 jobs (job sets of 32 bits up to 20
-// jobs, 64 bits up to 50) and 20 machines, and every front fits 16 bits (the sum of all
-// processing times does).
-// TTS_FRONT=0 turns it off (permutation nodes everywhere: A/B runs); the CPU and the
-// HIP module read the variable alike, so every engine of a process agrees.
-inline bool pfsp_front_ok(const PfspInstance& in, int lb) {
-  if (lb != 0 && lb != 1) return false;
-  if (const char* e = std::getenv("TTS_FRONT"))
-    if (e[0] == '0') return false;
-  if (in.jobs > 50 || in.machines > 20 || pfsp_machine_bucket(in.machines) == 0) return false;
-  long tot = 0;
-  for (int v : in.p) tot += v;
-  return tot < 65536;
-}
-
 // Every prefix completion time of the instance fits 16 bits: the condition of the
 // permutation-node kernels that pack a front into a u16 (the `front | remain << 16` LDS
 // words of the LB2 kernels and their u16 child fronts, csrc/hip/pfsp_kernels.hpp).
@@ -93,15 +78,52 @@ inline bool pfsp_fronts_fit_u16(const PfspInstance& in) {
   return std::min((in.jobs + in.machines - 1) * pmax, tot) < 65536;
 }
 
-// job bucket of the front layout: 20 (32-bit job sets) or 50 (64-bit)
-inline int pfsp_front_jobs(int jobs) { return jobs <= 20 ? 20 : 50; }
+// TTS_FRONT_WIDE=1 (CLI --front-wide): front nodes for 51-100 jobs too. Opt-in: without
+// it those instances keep their permutation nodes. Read wherever TTS_FRONT is, so the
+// CPU module, the HIP module and every spawned rank agree.
+inline bool pfsp_front_wide_wanted() {
+  const char* e = std::getenv("TTS_FRONT_WIDE");
+  return e != nullptr && e[0] == '1';
+}
+
+// The front layout applies: LB1 / LB1_d, at most 20 machines, and
+//   * up to 50 jobs (job sets of 32 bits up to 20 jobs, 64 bits up to 50): the sum of all
+//     processing times fits 16 bits, so every front does;
+//   * 51 to 100 jobs (128-bit job sets), only with TTS_FRONT_WIDE=1: the staircase rule
+//     pfsp_fronts_fit_u16, (jobs + machines - 1) * max p < 65536 (or the sum of all
+//     processing times, if smaller). The sum alone would exclude every 100 x 20 instance
+//     (ta081: sum 98,766, staircase 11,781). The staircase rule covers every 16-bit
+//     quantity of the front kernel, each being at most (jobs + machines - 1) * max p:
+//       - a front and a child's chain value are completion times: staircase paths of at
+//         most jobs + machines - 1 cells (the root's minimum heads cover fewer);
+//       - a remain is at most a machine's column sum (<= jobs cells), and remain + tail
+//         adds at most machines - 1 - m cells of one job;
+//       - a bound start_m + remain_m + tail_m covers at most (depth + m) + (jobs - depth) +
+//         (machines - 1 - m) = jobs + machines - 1 cells.
+// TTS_FRONT=0 turns every front layout off (permutation nodes everywhere: A/B runs); the
+// CPU and the HIP module read the variables alike, so every engine of a process agrees.
+inline bool pfsp_front_ok(const PfspInstance& in, int lb) {
+  if (lb != 0 && lb != 1) return false;
+  if (const char* e = std::getenv("TTS_FRONT"))
+    if (e[0] == '0') return false;
+  if (in.jobs > 50)
+    return in.jobs <= 100 && in.machines <= 20 && pfsp_machine_bucket(in.machines) != 0 && pfsp_front_wide_wanted() &&
+           pfsp_fronts_fit_u16(in);
+  if (in.jobs > 50 || in.machines > 20 || pfsp_machine_bucket(in.machines) == 0) return false;
+  long tot = 0;
+  for (int v : in.p) tot += v;
+  return tot < 65536;
+}
+
+// job bucket of the front layout: 20 (32-bit job sets), 50 (64-bit) or 100 (128-bit)
+inline int pfsp_front_jobs(int jobs) { return jobs <= 20 ? 20 : jobs <= 50 ? 50 : 100; }
 
 template <int MB, int NJ = 20>
 struct PfspFrontProblem {
   using Node = PfspFrontNode<MB, NJ>;
   using Mask = typename Node::Mask;
   static constexpr int kJobs = NJ;
-  static constexpr int kMaxJ = NJ <= 32 ? 32 : 64;
+  static constexpr int kMaxJ = NJ <= 32 ? 32 : NJ <= 64 ? 64 : 128;
   const PfspInstance* inst = nullptr;
   int lb = 1;
   int jobs = 0;
@@ -117,9 +139,7 @@ struct PfspFrontProblem {
       for (int m = 0; m < MB; ++m) p[j][m] = (j < in.jobs && m < in.machines) ? in.pt(m, j) : 0;
   }
 
-  Mask all_jobs() const {
-    return jobs >= static_cast<int>(8 * sizeof(Mask)) ? ~Mask(0) : ((Mask(1) << jobs) - Mask(1));
-  }
+  Mask all_jobs() const { return mask_first<Mask>(jobs); }
 
   Node root() const {
     Node r{};
@@ -132,7 +152,7 @@ struct PfspFrontProblem {
   // remain + tail of the parent's unscheduled jobs, per machine
   void remain_tail(const Node& n, int* r) const {
     for (int m = 0; m < MB; ++m) r[m] = tab.tails[m];
-    for (Mask x = n.rest; x; x &= x - 1) {
+    for (Mask x = n.rest; !mask_empty(x); mask_pop_low(x)) {
       const int j = mask_ctz(x);
       for (int m = 0; m < MB; ++m) r[m] += p[j][m];
     }
@@ -162,7 +182,7 @@ struct PfspFrontProblem {
   void children_bounds(const Node& n, int* lb_by_job) const {
     int r[MB];
     remain_tail(n, r);
-    for (Mask x = n.rest; x; x &= x - 1) {
+    for (Mask x = n.rest; !mask_empty(x); mask_pop_low(x)) {
       const int j = mask_ctz(x);
       lb_by_job[j] = child(n, r, j, nullptr);
     }
@@ -173,7 +193,7 @@ struct PfspFrontProblem {
     int r[MB];
     remain_tail(parent, r);
     const bool leaf = parent.depth + 1 == jobs;
-    for (Mask x = parent.rest; x; x &= x - 1) {
+    for (Mask x = parent.rest; !mask_empty(x); mask_pop_low(x)) {
       const int j = mask_ctz(x);
       Node c{};
       const int b = child(parent, r, j, leaf ? nullptr : c.front);
@@ -182,7 +202,8 @@ struct PfspFrontProblem {
         if (b < best) best = b;
       } else if (b < best) {
         c.depth = static_cast<uint8_t>(parent.depth + 1);
-        c.rest = parent.rest & ~(Mask(1) << j);
+        c.rest = parent.rest;
+        mask_clear(c.rest, j);
         push(c);
         ++tree;
       }
@@ -198,7 +219,6 @@ struct is_front_problem<PfspFrontProblem<MB, NJ>> : std::true_type {};
 // Front node of a permutation node (scheduled prefix prmu[0..depth)).
 template <int MB, int NJ, class PermNode>
 inline PfspFrontNode<MB, NJ> pfsp_front_from_perm(const PfspFrontProblem<MB, NJ>& prob, const PermNode& n) {
-  using Mask = typename PfspFrontNode<MB, NJ>::Mask;
   PfspFrontNode<MB, NJ> f{};
   f.depth = static_cast<uint8_t>(n.depth);
   f.rest = prob.all_jobs();
@@ -209,7 +229,7 @@ inline PfspFrontNode<MB, NJ> pfsp_front_from_perm(const PfspFrontProblem<MB, NJ>
   int fr[MB] = {};
   for (int i = 0; i < n.depth; ++i) {
     const int j = n.prmu[i];
-    f.rest &= ~(Mask(1) << j);
+    mask_clear(f.rest, j);
     fr[0] += prob.p[j][0];
     for (int m = 1; m < MB; ++m) fr[m] = std::max(fr[m - 1], fr[m]) + prob.p[j][m];
   }
@@ -230,10 +250,17 @@ decltype(auto) with_pfsp_problem(const PfspInstance& in, int lb, F&& f) {
         default: return f(PfspFrontProblem<20>(in, lb));
       }
     }
+    if (in.jobs <= 50) {
+      switch (pfsp_machine_bucket(in.machines)) {
+        case 5: return f(PfspFrontProblem<5, 50>(in, lb));
+        case 10: return f(PfspFrontProblem<10, 50>(in, lb));
+        default: return f(PfspFrontProblem<20, 50>(in, lb));
+      }
+    }
     switch (pfsp_machine_bucket(in.machines)) {
-      case 5: return f(PfspFrontProblem<5, 50>(in, lb));
-      case 10: return f(PfspFrontProblem<10, 50>(in, lb));
-      default: return f(PfspFrontProblem<20, 50>(in, lb));
+      case 5: return f(PfspFrontProblem<5, 100>(in, lb));
+      case 10: return f(PfspFrontProblem<10, 100>(in, lb));
+      default: return f(PfspFrontProblem<20, 100>(in, lb));
     }
   }
   return with_pfsp_bucket(in.jobs, [&](auto nj) -> decltype(auto) {

@@ -56,8 +56,125 @@ TTS_HD inline PfspNode<NJ> pfsp_child(const PfspNode<NJ>& parent, int k) {
   return c;
 }
 
-// Front-carrying node of the LB1 / LB1_d search on small instances (<= 32 jobs,
-// machine bucket MB in {5, 10, 20}). LB1 only depends on the scheduled prefix through
+// Job set wider than a machine word (front nodes above 64 jobs): W 64-bit words, low word
+// first, bit j of the set in bit j % 64 of word j / 64. A plain value type with the
+// handful of operations below — the hot loops never see a 128-bit integer, and never a
+// shift of the whole set by a variable amount: the kernels walk a set one 64-bit word at
+// a time (dev::mask_words).
+template <int W>
+struct JobSet {
+  uint64_t w[W];
+};
+
+// The set operations of the front layout, alike for the 32-bit, the 64-bit and the
+// multi-word sets: test / set / clear bit j, clear the lowest set bit, lowest set bit
+// (mask_ctz, of a non-empty set), popcount, popcount below bit j, the first n bits,
+// and-not, is-empty.
+TTS_HD inline bool mask_test(uint32_t x, int j) { return (x >> j) & 1u; }
+TTS_HD inline bool mask_test(uint64_t x, int j) { return (x >> j) & 1u; }
+TTS_HD inline void mask_set(uint32_t& x, int j) { x |= uint32_t(1) << j; }
+TTS_HD inline void mask_set(uint64_t& x, int j) { x |= uint64_t(1) << j; }
+TTS_HD inline void mask_clear(uint32_t& x, int j) { x &= ~(uint32_t(1) << j); }
+TTS_HD inline void mask_clear(uint64_t& x, int j) { x &= ~(uint64_t(1) << j); }
+TTS_HD inline void mask_pop_low(uint32_t& x) { x &= x - 1; }
+TTS_HD inline void mask_pop_low(uint64_t& x) { x &= x - 1; }
+TTS_HD inline int mask_ctz(uint32_t x) { return __builtin_ctz(x); }
+TTS_HD inline int mask_ctz(uint64_t x) { return __builtin_ctzll(x); }
+TTS_HD inline int mask_count(uint32_t x) { return __builtin_popcount(x); }
+TTS_HD inline int mask_count(uint64_t x) { return __builtin_popcountll(x); }
+TTS_HD inline int mask_count_below(uint32_t x, int j) { return __builtin_popcount(x & ((uint32_t(1) << j) - 1u)); }
+TTS_HD inline int mask_count_below(uint64_t x, int j) { return __builtin_popcountll(x & ((uint64_t(1) << j) - 1u)); }
+TTS_HD inline uint32_t mask_andnot(uint32_t a, uint32_t b) { return a & ~b; }
+TTS_HD inline uint64_t mask_andnot(uint64_t a, uint64_t b) { return a & ~b; }
+TTS_HD inline bool mask_empty(uint32_t x) { return x == 0; }
+TTS_HD inline bool mask_empty(uint64_t x) { return x == 0; }
+
+// (the word-wise forms: a bit index picks its word by comparison, never by a variable
+// index into w[], so a set held in registers stays there)
+template <int W>
+TTS_HD inline bool mask_test(const JobSet<W>& x, int j) {
+  uint64_t v = 0;
+  for (int k = 0; k < W; ++k) v = (j >> 6) == k ? x.w[k] : v;
+  return (v >> (j & 63)) & 1u;
+}
+template <int W>
+TTS_HD inline void mask_set(JobSet<W>& x, int j) {
+  const uint64_t b = uint64_t(1) << (j & 63);
+  for (int k = 0; k < W; ++k) x.w[k] |= (j >> 6) == k ? b : uint64_t(0);
+}
+template <int W>
+TTS_HD inline void mask_clear(JobSet<W>& x, int j) {
+  const uint64_t b = uint64_t(1) << (j & 63);
+  for (int k = 0; k < W; ++k) x.w[k] &= ~((j >> 6) == k ? b : uint64_t(0));
+}
+template <int W>
+TTS_HD inline void mask_pop_low(JobSet<W>& x) {
+  bool done = false;
+  for (int k = 0; k < W; ++k) {
+    const bool here = !done && x.w[k] != 0;
+    x.w[k] = here ? (x.w[k] & (x.w[k] - 1)) : x.w[k];
+    done = done || here;
+  }
+}
+template <int W>
+TTS_HD inline int mask_ctz(const JobSet<W>& x) {
+  for (int k = 0; k < W - 1; ++k)
+    if (x.w[k]) return 64 * k + __builtin_ctzll(x.w[k]);
+  return 64 * (W - 1) + __builtin_ctzll(x.w[W - 1]);
+}
+template <int W>
+TTS_HD inline int mask_count(const JobSet<W>& x) {
+  int c = 0;
+  for (int k = 0; k < W; ++k) c += __builtin_popcountll(x.w[k]);
+  return c;
+}
+template <int W>
+TTS_HD inline int mask_count_below(const JobSet<W>& x, int j) {
+  const uint64_t low = (uint64_t(1) << (j & 63)) - 1u;
+  int c = 0;
+  for (int k = 0; k < W; ++k) {
+    const uint64_t m = k < (j >> 6) ? ~uint64_t(0) : (k == (j >> 6) ? low : uint64_t(0));
+    c += __builtin_popcountll(x.w[k] & m);
+  }
+  return c;
+}
+template <int W>
+TTS_HD inline JobSet<W> mask_andnot(const JobSet<W>& a, const JobSet<W>& b) {
+  JobSet<W> r;
+  for (int k = 0; k < W; ++k) r.w[k] = a.w[k] & ~b.w[k];
+  return r;
+}
+template <int W>
+TTS_HD inline bool mask_empty(const JobSet<W>& x) {
+  uint64_t v = 0;
+  for (int k = 0; k < W; ++k) v |= x.w[k];
+  return v == 0;
+}
+
+// The first n bits (0 <= n <= bits of the set): the job set of an n-job root; with
+// n = the set's width, every bit.
+template <class Mask>
+struct MaskFirst {
+  TTS_HD static Mask get(int n) { return n >= static_cast<int>(8 * sizeof(Mask)) ? ~Mask(0) : ((Mask(1) << n) - Mask(1)); }
+};
+template <int W>
+struct MaskFirst<JobSet<W>> {
+  TTS_HD static JobSet<W> get(int n) {
+    JobSet<W> r;
+    for (int k = 0; k < W; ++k) {
+      const int b = n - 64 * k;
+      r.w[k] = b >= 64 ? ~uint64_t(0) : (b <= 0 ? uint64_t(0) : ((uint64_t(1) << b) - 1u));
+    }
+    return r;
+  }
+};
+template <class Mask>
+TTS_HD inline Mask mask_first(int n) {
+  return MaskFirst<Mask>::get(n);
+}
+
+// Front-carrying node of the LB1 / LB1_d search (machine bucket MB in {5, 10, 20}). LB1
+// only depends on the scheduled prefix through
 // its per-machine completion times (front) and on the set of unscheduled jobs, so the
 // node stores exactly that: a child costs O(M) from its parent instead of replaying
 // the O(depth * M) prefix chain (ref schedule_front, c_bound_simple.c:52-69, which
@@ -68,12 +185,19 @@ TTS_HD inline PfspNode<NJ> pfsp_child(const PfspNode<NJ>& parent, int k) {
 //   front[m]    completion time of the prefix on machine m; at the root the minimum
 //               heads (ref schedule_front with limit1 == -1)
 // NJ (job bucket of the front layout): 20 keeps the unscheduled set in 32 bits, 50 in
-// 64 (the set then starts at byte 8 and the fronts at byte 16).
+// 64 (the set then starts at byte 8 and the fronts at byte 16), 100 in a JobSet of two
+// 64-bit words (the set at byte 16, the fronts at byte 32: 48 / 64 / 80 B for 5 / 10 / 20
+// machines, where the permutation node is 112 B). One pattern for all: depth in byte 0,
+// padding to sizeof(Mask), the set, the u16 fronts.
+template <int NJ>
+using PfspJobMask =
+    std::conditional_t<(NJ <= 32), uint32_t, std::conditional_t<(NJ <= 64), uint64_t, JobSet<(NJ + 63) / 64>>>;
+
 template <int MB, int NJ = 20>
 struct alignas(16) PfspFrontNode {
   static constexpr int kMachines = MB;
   static constexpr int kJobs = NJ;
-  using Mask = std::conditional_t<(NJ <= 32), uint32_t, uint64_t>;
+  using Mask = PfspJobMask<NJ>;
   uint8_t depth;
   uint8_t pad[sizeof(Mask) - 1];
   Mask rest;
@@ -84,10 +208,12 @@ static_assert(sizeof(PfspFrontNode<5>) == 32 && sizeof(PfspFrontNode<10>) == 32 
 static_assert(sizeof(PfspFrontNode<5, 50>) == 32 && sizeof(PfspFrontNode<10, 50>) == 48 &&
                   sizeof(PfspFrontNode<20, 50>) == 64,
               "50-job front node sizes");
-
-// lowest set bit of a job set (32 or 64 bits)
-TTS_HD inline int mask_ctz(uint32_t x) { return __builtin_ctz(x); }
-TTS_HD inline int mask_ctz(uint64_t x) { return __builtin_ctzll(x); }
+static_assert(sizeof(JobSet<2>) == 16 && sizeof(PfspFrontNode<5, 100>) == 48 && sizeof(PfspFrontNode<10, 100>) == 64 &&
+                  sizeof(PfspFrontNode<20, 100>) == 80,
+              "100-job front node sizes");
+using PfspFrontNodeWidest = PfspFrontNode<20, 100>;
+static_assert(__builtin_offsetof(PfspFrontNodeWidest, rest) == 16 && __builtin_offsetof(PfspFrontNodeWidest, front) == 32,
+              "100-job front node: the set at byte 16, the fronts at byte 32");
 
 // Job-count buckets a run-time instance is dispatched to.
 inline int pfsp_bucket(int jobs) {

@@ -22,6 +22,7 @@ namespace tts {
 struct PfspArgs {
   int inst = 14, lb = 1, ub = 1, m = 25, M = 50000, T = 5000, D = 1, C = 1, ws = 1, L = 1;
   double perc = 0.5;
+  bool front_wide = false;  // --front-wide: front nodes for 51-100 jobs too (TTS_FRONT_WIDE=1)
 };
 
 inline PfspArgs parse_pfsp_args(int argc, char* argv[]) {
@@ -31,7 +32,8 @@ inline PfspArgs parse_pfsp_args(int argc, char* argv[]) {
                                          {"M", required_argument, nullptr, 'M'},    {"T", required_argument, nullptr, 'T'},
                                          {"D", required_argument, nullptr, 'D'},    {"C", required_argument, nullptr, 'C'},
                                          {"ws", required_argument, nullptr, 'w'},   {"L", required_argument, nullptr, 'L'},
-                                         {"perc", required_argument, nullptr, 'p'}, {nullptr, 0, nullptr, 0}};
+                                         {"perc", required_argument, nullptr, 'p'}, {"front-wide", no_argument, nullptr, 'F'},
+                                         {nullptr, 0, nullptr, 0}};
   int opt, idx = 0;
   auto fail = [](const char* msg) {
     std::fprintf(stderr, "%s\n", msg);
@@ -52,10 +54,12 @@ inline PfspArgs parse_pfsp_args(int argc, char* argv[]) {
       case 'w': if (v < 0 || v > 1) fail("Error: unsupported Intra-node Work Stealing option"); a.ws = v; break;
       case 'L': if (v < 0 || v > 1) fail("Error: unsupported distributed dynamic load balancing option"); a.L = v; break;
       case 'p': if (v <= 0 || v > 100) fail("Error: unsupported WS percentage for popFrontBulkFree"); a.perc = v / 100.0; break;
+      // set here, before any engine or rank exists: pfsp_front_ok reads it (core/pfsp_front.hpp)
+      case 'F': a.front_wide = true; setenv("TTS_FRONT_WIDE", "1", 1); break;
       default:
         std::fprintf(stderr,
                      "Usage: %s --inst <value> --lb <value> --ub <value> --m <value> --M <value> --T <value> --D <value> "
-                     "--C <value> --w <value> --L <value> --perc <value>\n",
+                     "--C <value> --w <value> --L <value> --perc <value> [--front-wide]\n",
                      argv[0]);
         std::exit(EXIT_FAILURE);
     }

@@ -73,7 +73,9 @@ struct PfspFrontTraits {
   // backlog anyway; 4K-parent windows were slower again: profiles/r4/local_min.txt)
   static constexpr int kLocalMin = 16384;
   static constexpr int kMaxChunks = G::MAXCHUNKS;
-  static constexpr bool kDyn = true;  // dynamic local DFS iterations (front_dyn)
+  // dynamic local DFS iterations (front_dyn): not for the 100-job bucket (off by default,
+  // measured slower everywhere; its donation protocol is not ported to the wider nodes)
+  static constexpr bool kDyn = G::DYN;
   // Does a launch with these arguments need the instrumented instantiation (the dynamic
   // local DFS or a probe)? Everything else runs the production one.
   static bool instrumented(const Args& a) { return a.pool.dyn || a.dbg_rec || a.dbg_blk; }
@@ -670,7 +672,7 @@ FrontProbeResult pfsp_front_probe_t(const PfspInstance& in, int lb, const void* 
     Node parent;
     std::memcpy(&parent, r + 2, sizeof(Node));
     bool bad = false;
-    if (j >= NJ || !((parent.rest >> j) & 1u)) {
+    if (j >= NJ || !mask_test(parent.rest, j)) {
       ++res.bad_job;
       bad = true;
     } else {
@@ -866,7 +868,7 @@ std::vector<double> pfsp_front_time_t(const PfspInstance& in, int lb, const void
   int dyn_us = cfg.dyn_us;
   if (const char* f = std::getenv("TTS_DYN_US")) dyn_us = std::max(0, std::atoi(f));
   const int dq = static_cast<int>(std::min<size_t>(dev::kDynQMax, max_chunks - std::min<size_t>(max_chunks, grid))) / 8 * 8;
-  if (dyn_us > 0 && dq >= 8) {
+  if (G::DYN && dyn_us > 0 && dq >= 8) {
     int rk = 0;
     TTS_HIP_CHECK(hipDeviceGetAttribute(&rk, hipDeviceAttributeWallClockRate, cfg.device));
     pa.dyn = static_cast<dev::DynCtl*>(dalloc(3 * sizeof(dev::DynCtl)));
@@ -930,7 +932,6 @@ std::vector<double> pfsp_front_time_t(const PfspInstance& in, int lb, const void
 template <int M, int NJ = 20>
 std::vector<int> pfsp_front_bounds_t(const PfspInstance& in, const PfspNode<NJ>* ph, size_t n, int device) {
   using FNode = PfspFrontNode<M, NJ>;
-  using Mask = typename FNode::Mask;
   TTS_HIP_CHECK(hipSetDevice(device));
   const PfspFrontProblem<M, NJ> prob(in, 1);
   std::vector<FNode> fn(n);
@@ -965,7 +966,7 @@ std::vector<int> pfsp_front_bounds_t(const PfspInstance& in, const PfspNode<NJ>*
     for (int k = d; k < in.jobs; ++k) {
       const int job = ph[i].prmu[k];
       out[offsets[i] + (k - d)] =
-          by_job[offsets[i] + __builtin_popcountll(static_cast<unsigned long long>(fn[i].rest & ((Mask(1) << job) - 1)))];
+          by_job[offsets[i] + mask_count_below(fn[i].rest, job)];
     }
   }
   return out;
@@ -990,7 +991,7 @@ std::vector<int> pfsp_expand_probe(const PfspInstance& in, int lb, const void* p
 std::vector<double> pfsp_front_time(const PfspInstance& in, int lb, const void* nodes, size_t n, int best,
                                     const EngineConfig& cfg, int reps);
 // front-layout instances only (pfsp_front_ok), defined with the 20-job bucket (the
-// 50-job front bucket's in its own TU)
+// 50-job and 100-job front buckets' in their own TUs)
 ExpandProbeResult pfsp_lb1_expand_probe(const PfspInstance& in, const void* parents, size_t n, int best, int device);
 FrontProbeResult pfsp_front_probe(const PfspInstance& in, int lb, const void* nodes, size_t n, int best,
                                   const EngineConfig& cfg, unsigned cap, int split_rank = 0, int split_world = 1,
@@ -1004,6 +1005,13 @@ FrontExpandResult pfsp_front_expand_probe(const PfspInstance& in, int lb, const 
                                           int device, bool production = false);
 FrontExpandResult pfsp_front_expand_probe_nj50(const PfspInstance& in, const void* nodes, size_t n, int best, int steps,
                                                int device, bool production);
+FrontProbeResult pfsp_front_probe_nj100(const PfspInstance& in, int lb, const void* nodes, size_t n, int best,
+                                        const EngineConfig& cfg, unsigned cap, int split_rank, int split_world,
+                                        size_t split_min);
+std::vector<double> pfsp_front_time_nj100(const PfspInstance& in, int lb, const void* nodes, size_t n, int best,
+                                          const EngineConfig& cfg, int reps);
+FrontExpandResult pfsp_front_expand_probe_nj100(const PfspInstance& in, const void* nodes, size_t n, int best, int steps,
+                                                int device, bool production);
 
 #define TTS_PFSP_DECLARE_BUCKET(NJ)                                                                   \
   std::unique_ptr<IEngine> make_pfsp_engine_nj##NJ(const PfspInstance& in, int lb, const EngineConfig& cfg); \
@@ -1025,7 +1033,7 @@ TTS_PFSP_DECLARE_BUCKET(500)
   std::unique_ptr<IEngine> make_pfsp_engine_nj##NJ(const PfspInstance& in, int lb, const EngineConfig& cfg) { \
     return with_machine_bucket(in.machines, [&](auto mm) -> std::unique_ptr<IEngine> {               \
       constexpr int M = decltype(mm)::value;                                                         \
-      if constexpr (NJ == 20 || NJ == 50)                                                            \
+      if constexpr (NJ == 20 || NJ == 50 || NJ == 100)                                               \
         if (pfsp_front_ok(in, lb)) return make_pfsp_front_engine_t<M, NJ>(in, cfg);                  \
       if (lb != 2) return make_pfsp_engine_t<NJ, M, 1>(in, cfg);                                    \
       if (M >= 10 && lb2_pk_wanted(in)) return make_pfsp_engine_t<NJ, M, 5>(in, cfg);                 \
@@ -1036,7 +1044,7 @@ TTS_PFSP_DECLARE_BUCKET(500)
                                           int device) {                                              \
     return with_machine_bucket(in.machines, [&](auto mm) {                                           \
       constexpr int M = decltype(mm)::value;                                                         \
-      if constexpr (NJ == 20 || NJ == 50)                                                            \
+      if constexpr (NJ == 20 || NJ == 50 || NJ == 100)                                               \
         if (pfsp_front_ok(in, lb))                                                                   \
           return pfsp_front_bounds_t<M, NJ>(in, static_cast<const PfspNode<NJ>*>(parents), n, device); \
       return lb == 2 ? pfsp_gpu_bounds_t<NJ, M, 2>(in, parents, n, best, device)                    \

@@ -35,17 +35,25 @@ namespace dev {
 
 template <int M, int NJ_ = 20>
 struct FrontGeom {
-  static constexpr int NJ = NJ_;                        // children per parent at most (job bucket 20 or 50)
+  static constexpr int NJ = NJ_;                        // children per parent at most (job bucket 20, 50 or 100)
   using Node = PfspFrontNode<M, NJ>;
-  using Mask = typename Node::Mask;                     // unscheduled-job set: 32 or 64 bits
-  static constexpr int MO = sizeof(Mask) / 4;           // first word of the set (1 or 2)
-  static constexpr int FO = 2 * MO;                     // first word of the fronts (2 or 4)
-  static constexpr int NW = sizeof(Node) / 4;           // node words in registers (8 or 12)
+  using Mask = typename Node::Mask;                     // unscheduled-job set: 32, 64 or 128 bits (JobSet<2>)
+  static constexpr int MO = sizeof(Mask) / 4;           // first word of the set (1, 2 or 4) = its 32-bit words
+  static constexpr int FO = 2 * MO;                     // first word of the fronts (2, 4 or 8)
+  static constexpr int NW = sizeof(Node) / 4;           // node words in registers (8 to 20)
   static constexpr int VPN = sizeof(Node) / 16;         // 16-B vectors per node
   static constexpr int BP = 256;                        // parents per chunk: one per thread
   static constexpr int MAXCH = BP * NJ;                 // children per chunk (upper bound)
   static constexpr int LT = 8;                          // local DFS steps per chunk at most
   static constexpr int SLOT = 2 * MAXCH;                // chunk slot region = its private stack
+  // (100 jobs: MAXCH 25,600 and SLOT 51,200 are past 2^15. Every per-chunk count and offset
+  // is an int — cnt / coff / the scans — and the 16-bit halves of the leaf word hold leaves
+  // and pushed-and-expanded nodes, both bounded by the nodes a chunk expands: LT * 256 in a
+  // local chunk, LMAX * 2 * CAP in a multi-level one, never by MAXCH)
+  static_assert(LT * BP < 65536, "the halves of the leaf word count expanded nodes");
+  // bits of the survivor count in the one-level kernel's combined scan (leaves above them)
+  static constexpr int SB = NJ <= 20 ? 13 : 15;
+  static_assert(BP * (NJ - 1) < (1 << SB) && SB + 9 < 31, "survivors of a chunk and its leaves (<= 256) share one scan word");
   static constexpr int MAXCHUNKS = 2048;
   // multi-level chunks (front_multi_level): up to BPF_CP parents, spread over the grid
   // (pool_begin), expanded LMAX levels deep at most; a level's survivors past CAP go out
@@ -67,7 +75,12 @@ struct FrontGeom {
   // (measured: a grid of 7 per CU with 6 resident made 256 workgroups start one workgroup
   // lifetime late, +1.3 us per wide iteration, +4 us per multi-level one)
   // (50-job nodes: 16 words for 20 machines, 12 for 10: 5 waves up to 10 machines)
-  static constexpr int WAVES = NJ > 20 ? (M <= 5 ? 6 : M <= 10 ? 5 : 4) : (M <= 10 ? 6 : 4);
+  // (100-job nodes, 12 / 16 / 20 words and a four-word set: 5 / 4 / 3, which is also what a
+  // CU's 160 KB of LDS holds of FrontSmem<M, 100>; 0 B scratch at these budgets,
+  // profiles/r9/kernel_resources.md)
+  static constexpr int WAVES = NJ > 50   ? (M <= 5 ? 5 : M <= 10 ? 4 : 3)
+                               : NJ > 20 ? (M <= 5 ? 6 : M <= 10 ? 5 : 4)
+                                         : (M <= 10 ? 6 : 4);
   // resident workgroups per CU the engine's grid is sized for: under the step priority one
   // below the register budget's 6 for 20-job, <= 10-machine instances (ta014 0.1840 ->
   // 0.1822 ms, 2/4/8-way shares -2..-4 %, ta008 3 engines +8 %; profiles/r5/grid_ab.txt)
@@ -85,6 +98,8 @@ struct FrontGeom {
   // the spread: profiles/r7/full_and_regress.txt; A/B builds: -DTTS_EMIT_BALANCED_MAXM=20)
   static constexpr int DW = 256;
   static constexpr bool BAL = M <= TTS_EMIT_BALANCED_MAXM;
+  // dynamic local DFS (front_dyn): the 20- and 50-job buckets only
+  static constexpr bool DYN = NJ <= 50;
 };
 
 template <int M, int NJ = 20>
@@ -180,6 +195,10 @@ struct FrontSmem {
   // (front_emit_balanced; a wave touches its own row only)
   uint16_t desc[kBlock / kWave][G::BAL ? G::DW : 1];
 };
+static_assert(FrontGeom<5, 100>::GRID_WGS * sizeof(FrontSmem<5, 100>) <= 160 * 1024 &&
+                  FrontGeom<10, 100>::GRID_WGS * sizeof(FrontSmem<10, 100>) <= 160 * 1024 &&
+                  FrontGeom<20, 100>::GRID_WGS * sizeof(FrontSmem<20, 100>) <= 160 * 1024,
+              "the 100-job grids' resident workgroups fit a CU's LDS");
 
 template <int M, int NJ>
 __device__ inline void front_row(const uint16_t* row, int (&pr)[M]) {
@@ -199,16 +218,58 @@ __device__ inline int front_of(const uint32_t (&w)[FrontGeom<M, NJ>::NW], int m)
   return static_cast<int>((w[FrontGeom<M, NJ>::FO + (m >> 1)] >> ((m & 1) * 16)) & 0xffffu);
 }
 
-// The unscheduled-job set of the node held in w (word 1, or words 2-3 for 50 jobs).
+// The unscheduled-job set of the node held in w (word 1, words 2-3 for 50 jobs, words 4-7
+// for 100).
 template <int M, int NJ>
 __device__ inline typename FrontGeom<M, NJ>::Mask front_mask(const uint32_t (&w)[FrontGeom<M, NJ>::NW]) {
-  if constexpr (FrontGeom<M, NJ>::MO == 1)
+  constexpr int MO = FrontGeom<M, NJ>::MO;
+  if constexpr (MO == 1) {
     return w[1];
-  else
+  } else if constexpr (MO == 2) {
     return static_cast<u64>(w[2]) | (static_cast<u64>(w[3]) << 32);
+  } else {
+    typename FrontGeom<M, NJ>::Mask x;
+#pragma unroll
+    for (int k = 0; k < MO / 2; ++k) x.w[k] = static_cast<u64>(w[MO + 2 * k]) | (static_cast<u64>(w[MO + 2 * k + 1]) << 32);
+    return x;
+  }
 }
-__device__ inline int mask_pop(uint32_t x) { return __popc(x); }
-__device__ inline int mask_pop(uint64_t x) { return __popcll(x); }
+// (the set's words of the node in c)
+template <int M, int NJ>
+__device__ inline void front_mask_put(const typename FrontGeom<M, NJ>::Mask& x, uint32_t (&c)[FrontGeom<M, NJ>::NW]) {
+  constexpr int MO = FrontGeom<M, NJ>::MO;
+  if constexpr (MO == 1) {
+    c[1] = x;
+  } else if constexpr (MO == 2) {
+    c[2] = static_cast<uint32_t>(x);
+    c[3] = static_cast<uint32_t>(static_cast<u64>(x) >> 32);
+  } else {
+#pragma unroll
+    for (int k = 0; k < MO / 2; ++k) {
+      c[MO + 2 * k] = static_cast<uint32_t>(x.w[k]);
+      c[MO + 2 * k + 1] = static_cast<uint32_t>(x.w[k] >> 32);
+    }
+  }
+}
+
+// f(x, base) for each machine word x of a job set in turn, base the job of its bit 0: the
+// loops over a set's jobs run one 64-bit word at a time (`for (; x; x &= x - 1)` on x,
+// job base + mask_ctz(x)), ascending. A one-word set is its own word. The words of a wider
+// set are picked by comparison in a loop that stays rolled: one copy of the body.
+template <class F>
+__device__ inline void mask_words(uint32_t x, F&& f) { f(x, 0); }
+template <class F>
+__device__ inline void mask_words(uint64_t x, F&& f) { f(x, 0); }
+template <int W, class F>
+__device__ inline void mask_words(const JobSet<W>& s, F&& f) {
+#pragma unroll 1
+  for (int k = 0; k < W; ++k) {
+    uint64_t x = s.w[0];
+#pragma unroll
+    for (int i = 1; i < W; ++i) x = k == i ? s.w[i] : x;
+    f(x, 64 * k);
+  }
+}
 
 template <int M, int NJ>
 __device__ inline void front_load(const PfspFrontNode<M, NJ>* src, uint32_t (&w)[FrontGeom<M, NJ>::NW]) {
@@ -250,8 +311,10 @@ __device__ inline void front_dbg(const PfspFrontArgs<M, NJ>& a, int kind, const 
 
 // Packed u16 pairs: two children's chains per VALU op (v_pk_max_u16 / v_pk_add_u16; the
 // p rows of the pair interleaved by one v_perm_b32 per machine). Every value of the chain
-// stays below 65536: the instance's processing times sum below it (pfsp_front_ok) and a
-// bound never exceeds a schedule's makespan.
+// stays below 65536 (pfsp_front_ok): up to 50 jobs the instance's processing times sum below
+// it and a bound never exceeds a schedule's makespan; for 51-100 jobs every front, chain
+// value, remain + tail and bound covers at most jobs + machines - 1 cells of the matrix
+// (the staircase rule, core/pfsp_front.hpp), and (jobs + machines - 1) * max p < 65536.
 
 // Bounds of the children appending the jobs of `rest` to a parent whose front / remain +
 // tail are fb[m] / rb[m] (each value in both halves): emit(j, lb) per job, ascending,
@@ -264,49 +327,53 @@ __device__ inline void front_bounds_x2(const FrontSmem<M, NJ>& sm, const uint32_
   // one child 9.31 s; on ta014's 10 machines the pairs win, 0.2245 -> 0.2209 ms:
   // profiles/r4/packed_bounds_ab.txt)
   if constexpr (M > 10) {
-    for (auto x = rest; x; x &= x - 1) {
-      const int j = mask_ctz(x);
-      int pr[M];
-      front_row<M, NJ>(sm.ptab[j], pr);
-      int lb = static_cast<int>(fb[0] & 0xffffu) + static_cast<int>(rb[0] & 0xffffu);
-      int tt = static_cast<int>(fb[0] & 0xffffu) + pr[0];
+    mask_words(rest, [&](auto x, int base) {
+      for (; x; x &= x - 1) {
+        const int j = base + mask_ctz(x);
+        int pr[M];
+        front_row<M, NJ>(sm.ptab[j], pr);
+        int lb = static_cast<int>(fb[0] & 0xffffu) + static_cast<int>(rb[0] & 0xffffu);
+        int tt = static_cast<int>(fb[0] & 0xffffu) + pr[0];
 #pragma unroll
-      for (int m = 1; m < M; ++m) {
-        const int sv = max(tt, static_cast<int>(fb[m] & 0xffffu));
-        lb = max(lb, sv + static_cast<int>(rb[m] & 0xffffu));
-        tt = sv + pr[m];
+        for (int m = 1; m < M; ++m) {
+          const int sv = max(tt, static_cast<int>(fb[m] & 0xffffu));
+          lb = max(lb, sv + static_cast<int>(rb[m] & 0xffffu));
+          tt = sv + pr[m];
+        }
+        emit(j, lb);
       }
-      emit(j, lb);
-    }
+    });
     return;
   }
-  for (auto x = rest; x;) {
-    const int j1 = mask_ctz(x);
-    x &= x - 1;
-    const bool two = x != 0;
-    const int j2 = two ? mask_ctz(x) : j1;
-    x &= x - 1;
-    const uint32_t* r1 = reinterpret_cast<const uint32_t*>(sm.ptab[j1]);
-    const uint32_t* r2 = reinterpret_cast<const uint32_t*>(sm.ptab[j2]);
-    uint32_t a[HW], b[HW];
+  mask_words(rest, [&](auto x, int base) {
+    while (x) {
+      const int j1 = base + mask_ctz(x);
+      x &= x - 1;
+      const bool two = x != 0;
+      const int j2 = two ? base + mask_ctz(x) : j1;
+      x &= x - 1;
+      const uint32_t* r1 = reinterpret_cast<const uint32_t*>(sm.ptab[j1]);
+      const uint32_t* r2 = reinterpret_cast<const uint32_t*>(sm.ptab[j2]);
+      uint32_t a[HW], b[HW];
 #pragma unroll
-    for (int h = 0; h < HW; ++h) {
-      a[h] = r1[h];
-      b[h] = r2[h];
-    }
-    u16x2 lb = as_u16x2(fb[0]) + as_u16x2(rb[0]);
-    u16x2 tt = as_u16x2(fb[0]) + as_u16x2(__builtin_amdgcn_perm(b[0], a[0], 0x05040100u));
+      for (int h = 0; h < HW; ++h) {
+        a[h] = r1[h];
+        b[h] = r2[h];
+      }
+      u16x2 lb = as_u16x2(fb[0]) + as_u16x2(rb[0]);
+      u16x2 tt = as_u16x2(fb[0]) + as_u16x2(__builtin_amdgcn_perm(b[0], a[0], 0x05040100u));
 #pragma unroll
-    for (int m = 1; m < M; ++m) {
-      const u16x2 pm = as_u16x2(__builtin_amdgcn_perm(b[m >> 1], a[m >> 1], (m & 1) ? 0x07060302u : 0x05040100u));
-      const u16x2 sv = __builtin_elementwise_max(tt, as_u16x2(fb[m]));
-      lb = __builtin_elementwise_max(lb, sv + as_u16x2(rb[m]));
-      tt = sv + pm;
+      for (int m = 1; m < M; ++m) {
+        const u16x2 pm = as_u16x2(__builtin_amdgcn_perm(b[m >> 1], a[m >> 1], (m & 1) ? 0x07060302u : 0x05040100u));
+        const u16x2 sv = __builtin_elementwise_max(tt, as_u16x2(fb[m]));
+        lb = __builtin_elementwise_max(lb, sv + as_u16x2(rb[m]));
+        tt = sv + pm;
+      }
+      const uint32_t l = as_u32(lb);
+      emit(j1, static_cast<int>(l & 0xffffu));
+      if (two) emit(j2, static_cast<int>(l >> 16));
     }
-    const uint32_t l = as_u32(lb);
-    emit(j1, static_cast<int>(l & 0xffffu));
-    if (two) emit(j2, static_cast<int>(l >> 16));
-  }
+  });
 }
 
 // fb / rb of a parent: its front (words of w) and its packed remain rp plus the tails
@@ -333,33 +400,37 @@ __device__ inline void front_remain(const FrontSmem<M, NJ>& sm, const uint32_t (
     // headline -0.9 % same box, profiles/r6/remain_ab.txt). 20 machines keep the rolled
     // loop (its registers are the kernel's budget).
     constexpr int U = 4;
-    for (auto x = front_mask<M, NJ>(w); x;) {
-      int j[U];
-      bool ok[U];
+    mask_words(front_mask<M, NJ>(w), [&](auto x, int base) {
+      while (x) {
+        int j[U];
+        bool ok[U];
 #pragma unroll
-      for (int u = 0; u < U; ++u) {
-        ok[u] = x != 0;
-        j[u] = ok[u] ? mask_ctz(x) : 0;
-        x &= x - 1;
+        for (int u = 0; u < U; ++u) {
+          ok[u] = x != 0;
+          j[u] = ok[u] ? base + mask_ctz(x) : 0;
+          x &= x - 1;
+        }
+        uint32_t rw[U][HW];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+          const uint32_t* row = reinterpret_cast<const uint32_t*>(sm.ptab[j[u]]);
+#pragma unroll
+          for (int h = 0; h < HW; ++h) rw[u][h] = row[h];
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u)
+#pragma unroll
+          for (int h = 0; h < HW; ++h) r2[h] += ok[u] ? rw[u][h] : 0u;
       }
-      uint32_t rw[U][HW];
-#pragma unroll
-      for (int u = 0; u < U; ++u) {
-        const uint32_t* row = reinterpret_cast<const uint32_t*>(sm.ptab[j[u]]);
-#pragma unroll
-        for (int h = 0; h < HW; ++h) rw[u][h] = row[h];
-      }
-#pragma unroll
-      for (int u = 0; u < U; ++u)
-#pragma unroll
-        for (int h = 0; h < HW; ++h) r2[h] += ok[u] ? rw[u][h] : 0u;
-    }
+    });
   } else {
-    for (auto x = front_mask<M, NJ>(w); x; x &= x - 1) {
-      const uint32_t* row = reinterpret_cast<const uint32_t*>(sm.ptab[mask_ctz(x)]);
+    mask_words(front_mask<M, NJ>(w), [&](auto x, int base) {
+      for (; x; x &= x - 1) {
+        const uint32_t* row = reinterpret_cast<const uint32_t*>(sm.ptab[base + mask_ctz(x)]);
 #pragma unroll
-      for (int h = 0; h < HW; ++h) r2[h] += row[h];
-    }
+        for (int h = 0; h < HW; ++h) r2[h] += row[h];
+      }
+    });
   }
 }
 
@@ -403,9 +474,9 @@ __device__ inline void front_child(const FrontSmem<M, NJ>& sm, const uint32_t (&
   c[0] = static_cast<uint32_t>(d + 1);
 #pragma unroll
   for (int i = 1; i < NW; ++i) c[i] = 0;
-  const auto rest = front_mask<M, NJ>(w) & ~(static_cast<typename FrontGeom<M, NJ>::Mask>(1) << j);
-  c[FrontGeom<M, NJ>::MO] = static_cast<uint32_t>(rest);
-  if constexpr (FrontGeom<M, NJ>::MO == 2) c[3] = static_cast<uint32_t>(static_cast<u64>(rest) >> 32);
+  auto rest = front_mask<M, NJ>(w);
+  mask_clear(rest, j);
+  front_mask_put<M, NJ>(rest, c);
   int ft = (root ? 0 : front_of<M, NJ>(w, 0)) + pr[0];
   c[FO] = static_cast<uint32_t>(ft);
 #pragma unroll
@@ -420,27 +491,32 @@ template <int M, int NJ, class Store>
 __device__ inline void front_emit_to(const FrontSmem<M, NJ>& sm, const uint32_t (&w)[FrontGeom<M, NJ>::NW],
                                      typename FrontGeom<M, NJ>::Mask surv,
                                      Store store) {
-  for (int i = 0; surv; ++i) {
-    const int j = mask_ctz(surv);
-    surv &= surv - 1;
-    uint32_t c[FrontGeom<M, NJ>::NW];
-    front_child<M, NJ>(sm, w, j, c);
-    store(i, c, j);
-  }
+  int i = 0;
+  mask_words(surv, [&](auto x, int base) {
+    for (; x; ++i) {
+      const int j = base + mask_ctz(x);
+      x &= x - 1;
+      uint32_t c[FrontGeom<M, NJ>::NW];
+      front_child<M, NJ>(sm, w, j, c);
+      store(i, c, j);
+    }
+  });
 }
 
 template <int M, int NJ>
 __device__ inline void front_emit(const FrontSmem<M, NJ>& sm, const uint32_t (&w)[FrontGeom<M, NJ>::NW],
                                   typename FrontGeom<M, NJ>::Mask surv,
                                   uint4* dst) {
-  while (surv) {
-    const int j = mask_ctz(surv);
-    surv &= surv - 1;
-    uint32_t c[FrontGeom<M, NJ>::NW];
-    front_child<M, NJ>(sm, w, j, c);
-    front_store<M, NJ>(dst, c);
-    dst += FrontGeom<M, NJ>::VPN;
-  }
+  mask_words(surv, [&](auto x, int base) {
+    while (x) {
+      const int j = base + mask_ctz(x);
+      x &= x - 1;
+      uint32_t c[FrontGeom<M, NJ>::NW];
+      front_child<M, NJ>(sm, w, j, c);
+      front_store<M, NJ>(dst, c);
+      dst += FrontGeom<M, NJ>::VPN;
+    }
+  });
 }
 
 // Wave-balanced emit: the survivors of a wave's 64 parents, one per lane and round,
@@ -476,9 +552,9 @@ __device__ inline void front_emit_balanced(FrontSmem<M, NJ>& sm, const uint32_t 
       // the next window of the list (the previous one's reads come first)
       __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
       __builtin_amdgcn_wave_barrier();
-      for (; surv && pos < s0 + DW; ++pos) {
+      for (; !mask_empty(surv) && pos < s0 + DW; ++pos) {
         desc[pos & (DW - 1)] = static_cast<uint16_t>((lane << 8) | mask_ctz(surv));
-        surv &= surv - 1;
+        mask_pop_low(surv);
       }
       __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
       __builtin_amdgcn_wave_barrier();
@@ -534,6 +610,24 @@ __device__ inline int kth_bit(uint64_t x, int k) {
   const int c = __popc(lo);
   return k < c ? kth_bit(lo, k) : 32 + kth_bit(static_cast<uint32_t>(x >> 32), k - c);
 }
+// (wider sets: the 32-bit word holding the bit is found first, low word first)
+template <int W>
+__device__ inline int kth_bit(const JobSet<W>& x, int k) {
+  uint32_t sel = 0;
+  int base = 0;
+  bool done = false;
+#pragma unroll
+  for (int i = 0; i < 2 * W; ++i) {
+    const uint32_t word = static_cast<uint32_t>(x.w[i >> 1] >> ((i & 1) * 32));
+    const int c = __popc(word);
+    const bool here = !done && k < c;
+    sel = here ? word : sel;
+    base = here ? 32 * i : base;
+    k = (done || here) ? k : k - c;
+    done = done || here;
+  }
+  return base + kth_bit(sel, k);
+}
 
 // Child-parallel expansion of n nodes staged in LDS (src[i], with their remain
 // rem[i]): ONE THREAD PER CHILD instead of one per parent. In a narrow level a
@@ -550,8 +644,14 @@ __device__ inline int front_child_offsets(FrontSmem<M, NJ>& sm, const uint4 (*sr
   int T = 0;
   int k = 0;
   if (static_cast<int>(threadIdx.x) < n) {
-    const uint4 h = src[threadIdx.x][0];  // the set: word 1 (20 jobs) or words 2-3 (50 jobs)
-    k = FrontGeom<M, NJ>::MO == 1 ? __popc(h.y) : __popc(h.z) + __popc(h.w);
+    // the set: word 1 (20 jobs) or words 2-3 (50 jobs) of vector 0, all of vector 1 (100 jobs)
+    if constexpr (FrontGeom<M, NJ>::MO == 4) {
+      const uint4 h = src[threadIdx.x][1];
+      k = __popc(h.x) + __popc(h.y) + __popc(h.z) + __popc(h.w);
+    } else {
+      const uint4 h = src[threadIdx.x][0];
+      k = FrontGeom<M, NJ>::MO == 1 ? __popc(h.y) : __popc(h.z) + __popc(h.w);
+    }
   }
   const int off = block_exclusive_scan(k, sm.scan, &T);
   if (static_cast<int>(threadIdx.x) < n) sm.coff[threadIdx.x] = off;
@@ -653,7 +753,7 @@ __device__ inline int front_expand_tp_regs(const A& a, FrontSmem<M, NJ>& sm,
                                            int best, int& nleaf, Store store, int kind = kDbgTp, Keep keep = {}) {
   using G = FrontGeom<M, NJ>;
   constexpr int HW = G::HW;
-  typename G::Mask surv = 0;
+  typename G::Mask surv{};
   int nsurv = 0;
   const bool leaf = static_cast<int>(w[0] & 0xffu) + 1 == a.jobs;
   {
@@ -667,7 +767,7 @@ __device__ inline int front_expand_tp_regs(const A& a, FrontSmem<M, NJ>& sm,
         if (lb < best) atomicMin(&a.pool.ctl->best.v, lb);
       } else if (kp && lb < best) {
         ++nsurv;
-        surv |= static_cast<typename G::Mask>(1) << j;
+        mask_set(surv, j);
       }
     });
   }
@@ -675,16 +775,18 @@ __device__ inline int front_expand_tp_regs(const A& a, FrontSmem<M, NJ>& sm,
   int idx = block_exclusive_scan(nsurv, sm.scan, &tot);
   // (the per-lane loop stays here: the balanced emit in this path too put the 10-machine
   // kernel over its 80 registers, 16 B of scratch: profiles/r7/kernel_resources.md)
-  while (surv) {
-    const int j = mask_ctz(surv);
-    surv &= surv - 1;
-    uint32_t cw[G::NW], cr[HW];
-    front_child<M, NJ>(sm, w, j, cw);
-    const uint32_t* row = reinterpret_cast<const uint32_t*>(sm.ptab[j]);
+  mask_words(surv, [&](auto x, int base) {
+    while (x) {
+      const int j = base + mask_ctz(x);
+      x &= x - 1;
+      uint32_t cw[G::NW], cr[HW];
+      front_child<M, NJ>(sm, w, j, cw);
+      const uint32_t* row = reinterpret_cast<const uint32_t*>(sm.ptab[j]);
 #pragma unroll
-    for (int h = 0; h < HW; ++h) cr[h] = rp[h] - row[h];
-    store(idx++, cw, cr);
-  }
+      for (int h = 0; h < HW; ++h) cr[h] = rp[h] - row[h];
+      store(idx++, cw, cr);
+    }
+  });
   return tot;
 }
 
@@ -785,8 +887,8 @@ __device__ inline void front_multi_level(const A& a, FrontSmem<M, NJ>& sm, const
       if (first) front_stamp(a, 4);
     } else {
       if (tid < n0) {
-        // the parent's remain: one pass over its unscheduled rows (packed u16 pairs; sums
-        // < 65536, pfsp_front_ok), by the thread that stages it
+        // the parent's remain: one pass over its unscheduled rows (packed u16 pairs; a
+        // machine's column sum < 65536, pfsp_front_ok), by the thread that stages it
         uint32_t w[G::NW], r2[G::HW];
         front_load<M, NJ>(pool_parent<Node, G::SLOT, G::MAXCHUNKS>(pa, v, t, g0 + tid, sm.pool), w);
         front_store<M, NJ>(&sm.lvl[tid][0], w);
@@ -910,7 +1012,7 @@ __device__ inline void front_local(const A& a, FrontSmem<M, NJ>& sm, const IterV
         }
         top -= npop;
       }
-      typename G::Mask surv = 0;
+      typename G::Mask surv{};
       int nsurv = 0;
       const bool leaf = static_cast<int>(w[0] & 0xffu) + 1 == a.jobs;
       if (!have_r) front_remain<M, NJ>(sm, w, rp);
@@ -922,7 +1024,7 @@ __device__ inline void front_local(const A& a, FrontSmem<M, NJ>& sm, const IterV
               if (lb < best) atomicMin(&pa.ctl->best.v, lb);
             } else if (lb < best) {
               ++nsurv;
-              surv |= static_cast<typename G::Mask>(1) << j;
+              mask_set(surv, j);
             }
           },
           kDbgLocal);
@@ -1418,7 +1520,7 @@ void pfsp_front_kernel(FrontArgsT<M, NJ, INSTR> a, int t) {
     ptv[i] = x < a.jobs * G::MS ? a.ptab[x] : 0;
   }
   const IterView v =
-      pool_begin<Node, G::MAXCHUNKS>(pa, t, G::BP, sm.pool, a.bpf, G::LT, G::NJ * (G::NJ - 1), G::LMAX, INSTR);
+      pool_begin<Node, G::MAXCHUNKS>(pa, t, G::BP, sm.pool, a.bpf, G::LT, G::NJ * (G::NJ - 1), G::LMAX, INSTR && G::DYN);
   front_stamp(a, 1);
   if (v.B == 0 || v.overflow) return;
   {
@@ -1434,7 +1536,7 @@ void pfsp_front_kernel(FrontArgsT<M, NJ, INSTR> a, int t) {
   pool_spill_leftovers<Node, G::SLOT, G::MAXCHUNKS>(pa, v, t, sm.pool);
   __syncthreads();
   front_stamp(a, 2);
-  if constexpr (INSTR) {
+  if constexpr (INSTR && G::DYN) {
     if (v.dyn) {
       front_dyn<M, NJ>(a, sm, v, t, best);
       front_stamp(a, 15);
@@ -1460,37 +1562,40 @@ void pfsp_front_kernel(FrontArgsT<M, NJ, INSTR> a, int t) {
     const bool leaf = static_cast<int>(w[0] & 0xffu) + 1 == a.jobs;
     // children this rank keeps (all of them outside the split iteration)
     using Mask = typename G::Mask;
-    Mask kmask = ~Mask(0);
+    Mask kmask = mask_first<Mask>(8 * sizeof(Mask));
     if (v.split) {
-      kmask = 0;
-      for (Mask x = front_mask<M, NJ>(w); x; x &= x - 1) {
-        const int j = mask_ctz(x);
-        kmask |= split_keep(v, gi, j) ? (Mask(1) << j) : Mask(0);
-      }
+      kmask = Mask{};
+      mask_words(front_mask<M, NJ>(w), [&](auto x, int base) {
+        for (; x; x &= x - 1) {
+          const int j = base + mask_ctz(x);
+          if (split_keep(v, gi, j)) mask_set(kmask, j);
+        }
+      });
     }
-    Mask surv = 0;
+    Mask surv{};
     int nsurv = 0, nleaf = 0;
     front_parent<M, NJ>(
         a, sm, w,
         [&](int j, int lb) {
-          const bool keep = (kmask >> j) & Mask(1);
+          const bool keep = mask_test(kmask, j);
           if (leaf) {
             nleaf += keep;
             if (lb < best) atomicMin(&pa.ctl->best.v, lb);
           } else if (keep && lb < best) {
             ++nsurv;
-            surv |= static_cast<typename G::Mask>(1) << j;
+            mask_set(surv, j);
           }
         },
         v.split ? kDbgSplit : kDbgOne);
     if (first) front_stamp(a, 4);
-    // one scan for both counts: survivors (<= 256 x 19) in bits 0-12, leaves (<= 256)
-    // in bits 13-21
+    // one scan for both counts: survivors (<= 256 x (NJ - 1)) in bits 0 to SB - 1 (13 bits
+    // for 20 jobs, 15 above), leaves (<= 256) in the 9 bits above them
     int tot = 0;
-    const int off = block_exclusive_scan(nsurv | (nleaf << 13), sm.scan, &tot) & 0x1fff;
+    constexpr int SB = G::SB;
+    const int off = block_exclusive_scan(nsurv | (nleaf << SB), sm.scan, &tot) & ((1 << SB) - 1);
     if (tid == 0) {
-      cnt_out[ch] = tot & 0x1fff;
-      lcnt_out[ch] = (tot >> 13) & 0x1ff;
+      cnt_out[ch] = tot & ((1 << SB) - 1);
+      lcnt_out[ch] = (tot >> SB) & 0x1ff;
     }
     if (first) front_stamp(a, 5);
     if constexpr (!G::BAL) {
@@ -1523,7 +1628,7 @@ __global__ __launch_bounds__(kBlock) void pfsp_front_bounds_kernel(PfspFrontArgs
     using Mask = typename G::Mask;
     const Mask rest = front_mask<M, NJ>(w);
     int* out = a.bounds_out + a.offsets[i];
-    front_parent<M, NJ>(a, sm, w, [&](int j, int lb) { out[mask_pop(rest & ((Mask(1) << j) - Mask(1)))] = lb; });
+    front_parent<M, NJ>(a, sm, w, [&](int j, int lb) { out[mask_count_below(rest, j)] = lb; });
   }
 }
 

@@ -3,8 +3,10 @@
 PFSP node (csrc/core/pfsp_node.hpp): id_t depth; id_t prmu[NJ]; padded to 16 B,
 id_t = uint8 for NJ <= 255 else uint16. PFSP front node (LB1 / LB1_d engines on up to
 20 jobs): uint8 depth, 3 pad, uint32 unscheduled-job mask, uint16 front[MB] (21-50 jobs:
-7 pad and a uint64 mask), padded
-to 16 B (32 B for MB <= 10 machines, 48 B for 20). N-Queens node: 4 x uint32
+7 pad and a uint64 mask; 51-100 jobs, with TTS_FRONT_WIDE=1: 15 pad and a 128-bit mask of
+two uint64 words, low word first), padded
+to 16 B (32 B for MB <= 10 machines, 48 B for 20; 50 jobs: 32 / 48 / 64 B and 100 jobs:
+48 / 64 / 80 B for 5 / 10 / 20 machines). N-Queens node: 4 x uint32
 {cols, diag, anti, depth}. Parity: ref pfsp/lib/PFSP_node.h:15-20 (44-B node with
 limit1 stored), nqueens/lib/NQueens_node.h:13-17 (board).
 """
@@ -61,17 +63,31 @@ def pfsp_root(jobs: int) -> np.ndarray:
 def pfsp_front_unpack(nodes: np.ndarray, machines_bucket: int, jobs: int = 20):
     """Front nodes -> (depths[n], rest masks[n], fronts[n, machines_bucket]). Up to 20
     jobs the unscheduled set is 32 bits at byte 4 and the fronts start at byte 8; up to
-    50 jobs it is 64 bits at byte 8 and the fronts start at byte 16."""
+    50 jobs it is 64 bits at byte 8 and the fronts start at byte 16; up to 100 jobs it is
+    128 bits at byte 16 (two uint64 words, low word first) and the fronts start at byte 32:
+    the masks then come back as an object array of Python ints, and pfsp_front_set_words
+    gives the two uint64 columns."""
     a = np.ascontiguousarray(nodes, dtype=np.uint8)
     depths = a[:, 0].astype(np.int64)
     if jobs <= 20:
         rest = a[:, 4:8].copy().view(np.uint32).reshape(-1).astype(np.int64)
         f0 = 8
+    elif jobs > 50:
+        w = pfsp_front_set_words(a)
+        rest = np.array([int(lo) | (int(hi) << 64) for lo, hi in w], dtype=object)
+        f0 = 32
     else:
         rest = a[:, 8:16].copy().view(np.uint64).reshape(-1)
         f0 = 16
     fronts = a[:, f0:f0 + 2 * machines_bucket].copy().view(np.uint16).astype(np.int64)
     return depths, rest, fronts
+
+
+def pfsp_front_set_words(nodes: np.ndarray) -> np.ndarray:
+    """The 128-bit unscheduled sets of 51-100-job front nodes as (n, 2) uint64 words, low
+    word first (bit j of the set: bit j % 64 of word j // 64)."""
+    a = np.ascontiguousarray(nodes, dtype=np.uint8)
+    return a[:, 16:32].copy().view(np.uint64).reshape(-1, 2)
 
 
 QUEENS_NODE_BYTES = 16
