@@ -484,4 +484,33 @@ PYBIND11_MODULE(_tts_hip, m) {
         return r;
       },
       py::arg("N"), py::arg("G"), py::arg("parents"), py::arg("device") = 0);
+  m.def(
+      "queens_expand_probe",
+      [](int N, int G, U8 nodes, int finish_k, int split_rank, int split_world, int device) {
+        if (nodes.ndim() != 2 || nodes.shape(1) != static_cast<py::ssize_t>(sizeof(QueensNode)))
+          throw std::invalid_argument("nodes must be a (n, 16) uint8 array");
+        QueensExpandResult r;
+        {
+          py::gil_scoped_release nogil;
+          r = queens_expand_probe(N, G, reinterpret_cast<const QueensNode*>(nodes.data()),
+                                  static_cast<size_t>(nodes.shape(0)), finish_k, split_rank, split_world, device);
+        }
+        constexpr size_t nb = sizeof(QueensNode);
+        U8 c({static_cast<py::ssize_t>(r.children.size() / nb), static_cast<py::ssize_t>(nb)});
+        if (!r.children.empty()) std::memcpy(c.mutable_data(), r.children.data(), r.children.size());
+        py::dict d;
+        d["children"] = c;
+        d["counts"] = r.counts;
+        d["leaves"] = r.leaves;
+        d["fin_tree"] = r.fin_tree;
+        d["fin_sol"] = r.fin_sol;
+        return d;
+      },
+      py::arg("N"), py::arg("G"), py::arg("nodes"), py::arg("finish_k") = 0, py::arg("split_rank") = 0,
+      py::arg("split_world") = 1, py::arg("device") = 0,
+      "ONE iteration of the production N-Queens kernel over these parents (the whole pool). Returns the children "
+      "of each output chunk in order, the per-chunk counts, the leaves counted and the tree / solution counts of "
+      "the subtrees finished inside the kernel (finish_k columns left at most; 0: none). split_world > 1: the "
+      "iteration is the rank split, this rank's share.");
+  m.def("queens_stack_nodes", &queens_stack_nodes, "Nodes per wave of the finishing stacks in this build.");
 }

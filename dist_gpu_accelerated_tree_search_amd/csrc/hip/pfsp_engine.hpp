@@ -21,6 +21,7 @@
 #include "engine.hpp"
 #include "pfsp_front_kernels.hpp"
 #include "pfsp_kernels.hpp"
+#include "probe_allocs.hpp"
 
 namespace tts {
 
@@ -695,25 +696,6 @@ FrontProbeResult pfsp_front_probe_t(const PfspInstance& in, int lb, const void* 
   }
   return res;
 }
-
-// Device allocations of a probe: freed on every exit path (a throwing HIP check included).
-struct ProbeAllocs {
-  std::vector<void*> owned;
-  ProbeAllocs() = default;
-  ProbeAllocs(const ProbeAllocs&) = delete;
-  ProbeAllocs& operator=(const ProbeAllocs&) = delete;
-  ~ProbeAllocs() {
-    for (void* d : owned) (void)hipFree(d);
-  }
-  // zeroed device memory
-  void* zeroed(size_t bytes) {
-    void* d = nullptr;
-    TTS_HIP_CHECK(hipMalloc(&d, std::max<size_t>(bytes, 16)));
-    owned.push_back(d);
-    TTS_HIP_CHECK(hipMemset(d, 0, std::max<size_t>(bytes, 16)));
-    return d;
-  }
-};
 
 // What ONE front-kernel iteration wrote (tests): the children of each output chunk in the
 // order the kernel laid them out, chunk after chunk. The bounds probe above checks what

@@ -1,7 +1,9 @@
 // N-Queens device engine (traits + factory) and reference-style label evaluation.
 #include <algorithm>
 #include <cstdlib>
+#include <stdexcept>
 
+#include "probe_allocs.hpp"
 #include "queens_engine.hpp"
 #include "queens_kernels.hpp"
 
@@ -58,6 +60,75 @@ static dev::QueensArgs queens_args(int N, int G) {
 std::unique_ptr<IEngine> make_queens_engine(int N, int G, const EngineConfig& cfg) {
   TTS_HIP_CHECK(hipSetDevice(cfg.device));
   return std::make_unique<DeviceEngine<QueensTraits>>(cfg, queens_args(N, G));
+}
+
+int queens_stack_nodes() { return dev::kQStack; }
+
+QueensExpandResult queens_expand_probe(int N, int G, const QueensNode* nodes, size_t n, int finish_k, int split_rank,
+                                       int split_world, int device) {
+  using S = dev::QueensSmem;
+  if (split_world > 1 && (split_rank < 0 || split_rank >= split_world))
+    throw std::invalid_argument("queens expand probe: split_rank outside [0, split_world)");
+  TTS_HIP_CHECK(hipSetDevice(device));
+  dev::QueensArgs a = queens_args(N, G);
+  a.finish_k = std::max(0, std::min(finish_k, dev::kQueensFinishMax));  // (not the environment's)
+  // the finishing stacks rely on depth == queens placed (at most finish_k children per stacked node)
+  for (size_t i = 0; i < n; ++i)
+    if (static_cast<int>(nodes[i].depth) > N || __builtin_popcount(nodes[i].cols) != static_cast<int>(nodes[i].depth) ||
+        (nodes[i].cols & ~a.full))
+      throw std::invalid_argument("queens expand probe: a node's depth is not the number of its placed queens");
+  QueensExpandResult res;
+  if (n == 0) return res;
+  const size_t nchunks = (n + S::BP - 1) / S::BP;
+  if (nchunks > static_cast<size_t>(S::MAXCHUNKS)) throw std::invalid_argument("queens expand probe: too many parents");
+  ProbeAllocs mem;
+  size_t cap = 1;
+  while (cap < n) cap *= 2;
+  auto& pa = a.pool;
+  pa.ring = static_cast<QueensNode*>(mem.zeroed(cap * sizeof(QueensNode)));
+  TTS_HIP_CHECK(hipMemcpy(pa.ring, nodes, n * sizeof(QueensNode), hipMemcpyHostToDevice));
+  for (int b = 0; b < 2; ++b) {
+    pa.buf[b] = static_cast<QueensNode*>(mem.zeroed(nchunks * S::MAXCH * sizeof(QueensNode)));
+    pa.cnt[b] = static_cast<int*>(mem.zeroed(nchunks * sizeof(int)));
+    pa.lcnt[b] = static_cast<int*>(mem.zeroed(nchunks * sizeof(int)));
+  }
+  dev::PoolCtl h{};
+  h.slot[0].stack = n;
+  if (split_world > 1) {
+    // the window holds the whole pool and at least split_min parents: this iteration splits
+    h.split_world = split_world;
+    h.split_rank = split_rank;
+    h.split_min = 1;
+  }
+  pa.ctl = static_cast<dev::PoolCtl*>(mem.zeroed(sizeof(dev::PoolCtl)));
+  TTS_HIP_CHECK(hipMemcpy(pa.ctl, &h, sizeof(h), hipMemcpyHostToDevice));
+  pa.cap_mask = cap - 1;
+  pa.max_parents = static_cast<int>(nchunks * S::BP);
+  pa.max_chunks = static_cast<int>(nchunks);
+  QueensTraits::launch(a, 0, static_cast<int>(nchunks), 0);
+  TTS_HIP_CHECK(hipGetLastError());
+  TTS_HIP_CHECK(hipDeviceSynchronize());
+  std::vector<int> lcnt(nchunks);
+  res.counts.assign(nchunks, 0);
+  TTS_HIP_CHECK(hipMemcpy(res.counts.data(), pa.cnt[1], nchunks * sizeof(int), hipMemcpyDeviceToHost));
+  TTS_HIP_CHECK(hipMemcpy(lcnt.data(), pa.lcnt[1], nchunks * sizeof(int), hipMemcpyDeviceToHost));
+  for (size_t c = 0; c < nchunks; ++c) {
+    if (res.counts[c] < 0 || res.counts[c] > S::MAXCH)
+      throw std::runtime_error("queens expand probe: chunk count out of range");
+    const size_t at = res.children.size(), bytes = static_cast<size_t>(res.counts[c]) * sizeof(QueensNode);
+    res.children.resize(at + bytes);
+    if (bytes)
+      TTS_HIP_CHECK(hipMemcpy(res.children.data() + at, pa.buf[1] + c * S::MAXCH, bytes, hipMemcpyDeviceToHost));
+    // (the whole leaf word: this kernel has no inner half)
+    res.leaves += static_cast<uint32_t>(lcnt[c]);
+  }
+  TTS_HIP_CHECK(hipMemcpy(&h, pa.ctl, sizeof(h), hipMemcpyDeviceToHost));
+  if (h.overflow) throw std::runtime_error("queens expand probe: the iteration reported an overflow");
+  for (const auto& x : h.xacc) {
+    res.fin_tree += x.tree;
+    res.fin_sol += x.sol;
+  }
+  return res;
 }
 
 std::vector<uint8_t> queens_gpu_labels(int N, int G, const QueensNode* parents, size_t n, int device) {

@@ -1,6 +1,10 @@
-"""N-Queens subtree finishing (csrc/hip/queens_kernels.hpp queens_dfs): parents with at
-most TTS_QUEENS_FINISH columns left are explored to the end by their own thread. Every
-finishing depth must give the level-by-level tree and solution counts."""
+"""N-Queens subtree finishing (csrc/hip/queens_kernels.hpp queens_finish_wave): parents
+with at most TTS_QUEENS_FINISH columns left are explored to the end inside the kernel —
+a wave's finishing parents go on its LDS stack and every pass bounds up to 64 stacked
+nodes, one per lane; a node whose children do not fit the stack is walked in registers by
+its lane (queens_dfs). Every finishing depth must give the level-by-level tree and
+solution counts. What one iteration writes and counts, on boards up to N = 32 and on
+inputs known to fit or to overflow the stack: tests/test_gpu_queens_probe.py."""
 import pytest
 
 from dist_gpu_accelerated_tree_search_amd import EngineOptions, QueensModel, solve_engine
