@@ -3,7 +3,7 @@
 #include <cstdlib>
 #include <stdexcept>
 
-#include "probe_allocs.hpp"
+#include "probe_pool.hpp"
 #include "queens_engine.hpp"
 #include "queens_kernels.hpp"
 
@@ -81,48 +81,23 @@ QueensExpandResult queens_expand_probe(int N, int G, const QueensNode* nodes, si
   if (n == 0) return res;
   const size_t nchunks = (n + S::BP - 1) / S::BP;
   if (nchunks > static_cast<size_t>(S::MAXCHUNKS)) throw std::invalid_argument("queens expand probe: too many parents");
-  ProbeAllocs mem;
-  size_t cap = 1;
-  while (cap < n) cap *= 2;
-  auto& pa = a.pool;
-  pa.ring = static_cast<QueensNode*>(mem.zeroed(cap * sizeof(QueensNode)));
-  TTS_HIP_CHECK(hipMemcpy(pa.ring, nodes, n * sizeof(QueensNode), hipMemcpyHostToDevice));
-  for (int b = 0; b < 2; ++b) {
-    pa.buf[b] = static_cast<QueensNode*>(mem.zeroed(nchunks * S::MAXCH * sizeof(QueensNode)));
-    pa.cnt[b] = static_cast<int*>(mem.zeroed(nchunks * sizeof(int)));
-    pa.lcnt[b] = static_cast<int*>(mem.zeroed(nchunks * sizeof(int)));
-  }
   dev::PoolCtl h{};
-  h.slot[0].stack = n;
   if (split_world > 1) {
     // the window holds the whole pool and at least split_min parents: this iteration splits
     h.split_world = split_world;
     h.split_rank = split_rank;
     h.split_min = 1;
   }
-  pa.ctl = static_cast<dev::PoolCtl*>(mem.zeroed(sizeof(dev::PoolCtl)));
-  TTS_HIP_CHECK(hipMemcpy(pa.ctl, &h, sizeof(h), hipMemcpyHostToDevice));
-  pa.cap_mask = cap - 1;
-  pa.max_parents = static_cast<int>(nchunks * S::BP);
-  pa.max_chunks = static_cast<int>(nchunks);
+  ProbeAllocs mem;
+  const ProbePool<QueensNode> pool(mem, a.pool, nodes, n, nchunks, S::MAXCH, S::BP, h);
   QueensTraits::launch(a, 0, static_cast<int>(nchunks), 0);
   TTS_HIP_CHECK(hipGetLastError());
   TTS_HIP_CHECK(hipDeviceSynchronize());
-  std::vector<int> lcnt(nchunks);
-  res.counts.assign(nchunks, 0);
-  TTS_HIP_CHECK(hipMemcpy(res.counts.data(), pa.cnt[1], nchunks * sizeof(int), hipMemcpyDeviceToHost));
-  TTS_HIP_CHECK(hipMemcpy(lcnt.data(), pa.lcnt[1], nchunks * sizeof(int), hipMemcpyDeviceToHost));
-  for (size_t c = 0; c < nchunks; ++c) {
-    if (res.counts[c] < 0 || res.counts[c] > S::MAXCH)
-      throw std::runtime_error("queens expand probe: chunk count out of range");
-    const size_t at = res.children.size(), bytes = static_cast<size_t>(res.counts[c]) * sizeof(QueensNode);
-    res.children.resize(at + bytes);
-    if (bytes)
-      TTS_HIP_CHECK(hipMemcpy(res.children.data() + at, pa.buf[1] + c * S::MAXCH, bytes, hipMemcpyDeviceToHost));
-    // (the whole leaf word: this kernel has no inner half)
-    res.leaves += static_cast<uint32_t>(lcnt[c]);
-  }
-  TTS_HIP_CHECK(hipMemcpy(&h, pa.ctl, sizeof(h), hipMemcpyDeviceToHost));
+  ProbeChunks ch = pool.read_chunks(nchunks, "queens expand probe");
+  res.children = std::move(ch.children);
+  res.counts = std::move(ch.counts);
+  for (int w : ch.lwords) res.leaves += static_cast<uint32_t>(w);  // (the whole leaf word: this kernel has no inner half)
+  h = pool.ctl();
   if (h.overflow) throw std::runtime_error("queens expand probe: the iteration reported an overflow");
   for (const auto& x : h.xacc) {
     res.fin_tree += x.tree;
@@ -136,21 +111,15 @@ std::vector<uint8_t> queens_gpu_labels(int N, int G, const QueensNode* parents, 
   dev::QueensArgs a = queens_args(N, G);
   std::vector<uint8_t> out(n * static_cast<size_t>(N), 0);
   if (n == 0) return out;
-  QueensNode* dp = nullptr;
-  uint8_t* dl = nullptr;
-  TTS_HIP_CHECK(hipMalloc(&dp, n * sizeof(QueensNode)));
-  TTS_HIP_CHECK(hipMalloc(&dl, out.size()));
-  TTS_HIP_CHECK(hipMemcpy(dp, parents, n * sizeof(QueensNode), hipMemcpyHostToDevice));
-  a.parents_in = dp;
-  a.labels_out = dl;
+  ProbeAllocs mem;
+  a.parents_in = mem.upload(parents, n);
+  a.labels_out = mem.alloc<uint8_t>(out.size());
   a.nparents = static_cast<int>(n);
   const int blocks = static_cast<int>((n + dev::kBlock - 1) / dev::kBlock);
   hipLaunchKernelGGL(dev::queens_labels_kernel, dim3(blocks), dim3(dev::kBlock), 0, 0, a);
   TTS_HIP_CHECK(hipGetLastError());
   TTS_HIP_CHECK(hipDeviceSynchronize());
-  TTS_HIP_CHECK(hipMemcpy(out.data(), dl, out.size(), hipMemcpyDeviceToHost));
-  (void)hipFree(dp);
-  (void)hipFree(dl);
+  TTS_HIP_CHECK(hipMemcpy(out.data(), a.labels_out, out.size(), hipMemcpyDeviceToHost));
   return out;
 }
 
