@@ -68,6 +68,10 @@ def _pfsp_parser(cls=argparse.ArgumentParser) -> argparse.ArgumentParser:
     ap.add_argument("--front-wide", action="store_true",
                     help="LB1 / LB1_d on 51-100 jobs: front-carrying nodes with 128-bit job sets instead of "
                          "permutation nodes (sets TTS_FRONT_WIDE=1 for this process and every rank it spawns)")
+    ap.add_argument("--front-all", action="store_true",
+                    help="LB1 / LB1_d on 51-500 jobs: front-carrying nodes (256- and 512-bit job sets above 100 "
+                         "jobs) instead of permutation nodes; includes --front-wide (sets TTS_FRONT_WIDE=2 for "
+                         "this process and every rank it spawns)")
     ap.add_argument("--json", default=None, help="append a JSON run record to this file")
     ap.add_argument("--csv-dir", default=".", help="directory of the CSV statistics files")
     ap.add_argument("--no-csv", action="store_true")
@@ -175,9 +179,9 @@ def pfsp_main(argv: list[str]) -> int:
     _validate_pfsp(a)
     if a.heuristic_ub:
         os.environ.setdefault("TTS_DIVE", "32")  # models.pfsp.PfspModel.search_best
-    if a.front_wide:
+    if a.front_wide or a.front_all:
         # before any model, engine or rank exists: csrc/core/pfsp_front.hpp pfsp_front_ok reads it
-        os.environ["TTS_FRONT_WIDE"] = "1"
+        os.environ["TTS_FRONT_WIDE"] = "2" if a.front_all else "1"
     from .models.pfsp import EngineOptions, PfspModel
     from .search import solve_cpu, solve_engine
 
@@ -376,11 +380,12 @@ def main(argv: list[str] | None = None) -> int:
         sys.stderr.write(__doc__ or "")
         return 2
     if argv[0] == "pfsp":
-        # --front-wide reaches the ranks through the environment, and they inherit the
-        # forkserver's: set it before that exists (pfsp_main sets it again for direct callers)
+        # --front-wide / --front-all reach the ranks through the environment, and they inherit
+        # the forkserver's: set it before that exists (pfsp_main sets it again for direct callers)
         try:
-            if _pfsp_parser(_QuietParser).parse_args(argv[1:]).front_wide:
-                os.environ["TTS_FRONT_WIDE"] = "1"
+            early = _pfsp_parser(_QuietParser).parse_args(argv[1:])
+            if early.front_wide or early.front_all:
+                os.environ["TTS_FRONT_WIDE"] = "2" if early.front_all else "1"
         except (ValueError, SystemExit):
             pass
     if _spawn_planned(argv):

@@ -213,6 +213,42 @@ PYBIND11_MODULE(_tts_cpu, m) {
         return out;
       },
       py::arg("inst"), py::arg("lb"), py::arg("nodes"));
+  m.def(
+      "pfsp_front_expand",
+      [](const PfspInstance& in, int lb, U8 nodes, int best) {
+        // one expansion of front-layout nodes against a fixed incumbent (PfspFrontProblem::
+        // decompose with a copy of `best` per parent): the host twin of one front-kernel
+        // iteration, for tests on buckets whose children number 10^5
+        return with_pfsp_problem(in, lb, [&](auto prob) -> py::tuple {
+          using P = decltype(prob);
+          if constexpr (is_front_problem<P>::value) {
+            using Node = typename P::Node;
+            size_t n = 0;
+            const Node* p = array_nodes<Node>(nodes, n);
+            std::vector<Node> kids;
+            unsigned long long tree = 0, sol = 0;
+            int low = INT_MAX;
+            for (size_t i = 0; i < n; ++i) {
+              int b = best;  // leaves do not lower the incumbent the siblings are pruned with
+              prob.decompose(p[i], b, tree, sol, [&](const Node& c) { kids.push_back(c); });
+              if (p[i].depth + 1 == prob.jobs) {
+                int rt[P::Node::kMachines];
+                prob.remain_tail(p[i], rt);
+                for (auto x = p[i].rest; !mask_empty(x); mask_pop_low(x))
+                  low = std::min(low, prob.child(p[i], rt, mask_ctz(x), nullptr));
+              }
+            }
+            py::object lo = py::none();
+            if (sol > 0) lo = py::int_(low);
+            return py::make_tuple(nodes_to_array(kids.data(), kids.size()), sol, lo);
+          } else {
+            throw std::invalid_argument("pfsp_front_expand: front layout only");
+          }
+        });
+      },
+      py::arg("inst"), py::arg("lb"), py::arg("nodes"), py::arg("best"),
+      "One expansion of front-layout nodes against the fixed incumbent `best`: (surviving children's bytes, "
+      "parents in order and jobs ascending; leaves evaluated; the lowest leaf bound or None).");
   m.def("queens_node_bytes", []() { return sizeof(QueensNode); });
 
   // ---- end-to-end CPU drivers ----

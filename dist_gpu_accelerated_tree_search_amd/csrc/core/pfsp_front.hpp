@@ -81,9 +81,12 @@ inline bool pfsp_fronts_fit_u16(const PfspInstance& in) {
 // TTS_FRONT_WIDE=1 (CLI --front-wide): front nodes for 51-100 jobs too. Opt-in: without
 // it those instances keep their permutation nodes. Read wherever TTS_FRONT is, so the
 // CPU module, the HIP module and every spawned rank agree.
-inline bool pfsp_front_wide_wanted() {
+// TTS_FRONT_WIDE=2 (CLI --front-all): front nodes for 51-500 jobs, so it includes what 1
+// does; 1 keeps meaning exactly 51-100.
+inline int pfsp_front_wide_level() {
   const char* e = std::getenv("TTS_FRONT_WIDE");
-  return e != nullptr && e[0] == '1';
+  if (e == nullptr) return 0;
+  return e[0] == '1' ? 1 : e[0] == '2' ? 2 : 0;
 }
 
 // The front layout applies: LB1 / LB1_d, at most 20 machines, and
@@ -100,6 +103,11 @@ inline bool pfsp_front_wide_wanted() {
 //         adds at most machines - 1 - m cells of one job;
 //       - a bound start_m + remain_m + tail_m covers at most (depth + m) + (jobs - depth) +
 //         (machines - 1 - m) = jobs + machines - 1 cells.
+//   * 101 to 500 jobs (256- and 512-bit job sets), only with TTS_FRONT_WIDE=2: the same
+//     staircase rule, and the same argument cell for cell (none of its three counts depends
+//     on the job range). With p <= 99: 200 x 20 gives 219 * 99 = 21,681 and 500 x 20 gives
+//     519 * 99 = 51,381, so all of ta091-ta120 are accepted; a machine's column sum is at
+//     most 500 * 99 = 49,500.
 // TTS_FRONT=0 turns every front layout off (permutation nodes everywhere: A/B runs); the
 // CPU and the HIP module read the variables alike, so every engine of a process agrees.
 inline bool pfsp_front_ok(const PfspInstance& in, int lb) {
@@ -107,23 +115,24 @@ inline bool pfsp_front_ok(const PfspInstance& in, int lb) {
   if (const char* e = std::getenv("TTS_FRONT"))
     if (e[0] == '0') return false;
   if (in.jobs > 50)
-    return in.jobs <= 100 && in.machines <= 20 && pfsp_machine_bucket(in.machines) != 0 && pfsp_front_wide_wanted() &&
-           pfsp_fronts_fit_u16(in);
+    return in.jobs <= 500 && in.machines <= 20 && pfsp_machine_bucket(in.machines) != 0 &&
+           pfsp_front_wide_level() >= (in.jobs <= 100 ? 1 : 2) && pfsp_fronts_fit_u16(in);
   if (in.jobs > 50 || in.machines > 20 || pfsp_machine_bucket(in.machines) == 0) return false;
   long tot = 0;
   for (int v : in.p) tot += v;
   return tot < 65536;
 }
 
-// job bucket of the front layout: 20 (32-bit job sets), 50 (64-bit) or 100 (128-bit)
-inline int pfsp_front_jobs(int jobs) { return jobs <= 20 ? 20 : jobs <= 50 ? 50 : 100; }
+// job bucket of the front layout: 20 (32-bit job sets), 50 (64-bit), 100 (128-bit), 200
+// (256-bit) or 500 (512-bit)
+inline int pfsp_front_jobs(int jobs) { return jobs <= 20 ? 20 : jobs <= 50 ? 50 : jobs <= 100 ? 100 : jobs <= 200 ? 200 : 500; }
 
 template <int MB, int NJ = 20>
 struct PfspFrontProblem {
   using Node = PfspFrontNode<MB, NJ>;
   using Mask = typename Node::Mask;
   static constexpr int kJobs = NJ;
-  static constexpr int kMaxJ = NJ <= 32 ? 32 : NJ <= 64 ? 64 : 128;
+  static constexpr int kMaxJ = 8 * static_cast<int>(sizeof(Mask));  // the set's width
   const PfspInstance* inst = nullptr;
   int lb = 1;
   int jobs = 0;
@@ -201,7 +210,7 @@ struct PfspFrontProblem {
         ++sol;
         if (b < best) best = b;
       } else if (b < best) {
-        c.depth = static_cast<uint8_t>(parent.depth + 1);
+        c.depth = static_cast<typename Node::depth_t>(parent.depth + 1);
         c.rest = parent.rest;
         mask_clear(c.rest, j);
         push(c);
@@ -220,7 +229,7 @@ struct is_front_problem<PfspFrontProblem<MB, NJ>> : std::true_type {};
 template <int MB, int NJ, class PermNode>
 inline PfspFrontNode<MB, NJ> pfsp_front_from_perm(const PfspFrontProblem<MB, NJ>& prob, const PermNode& n) {
   PfspFrontNode<MB, NJ> f{};
-  f.depth = static_cast<uint8_t>(n.depth);
+  f.depth = static_cast<typename PfspFrontNode<MB, NJ>::depth_t>(n.depth);
   f.rest = prob.all_jobs();
   if (n.depth == 0) {
     for (int m = 0; m < MB; ++m) f.front[m] = static_cast<uint16_t>(prob.tab.heads[m]);
@@ -257,10 +266,24 @@ decltype(auto) with_pfsp_problem(const PfspInstance& in, int lb, F&& f) {
         default: return f(PfspFrontProblem<20, 50>(in, lb));
       }
     }
+    if (in.jobs <= 100) {
+      switch (pfsp_machine_bucket(in.machines)) {
+        case 5: return f(PfspFrontProblem<5, 100>(in, lb));
+        case 10: return f(PfspFrontProblem<10, 100>(in, lb));
+        default: return f(PfspFrontProblem<20, 100>(in, lb));
+      }
+    }
+    if (in.jobs <= 200) {
+      switch (pfsp_machine_bucket(in.machines)) {
+        case 5: return f(PfspFrontProblem<5, 200>(in, lb));
+        case 10: return f(PfspFrontProblem<10, 200>(in, lb));
+        default: return f(PfspFrontProblem<20, 200>(in, lb));
+      }
+    }
     switch (pfsp_machine_bucket(in.machines)) {
-      case 5: return f(PfspFrontProblem<5, 100>(in, lb));
-      case 10: return f(PfspFrontProblem<10, 100>(in, lb));
-      default: return f(PfspFrontProblem<20, 100>(in, lb));
+      case 5: return f(PfspFrontProblem<5, 500>(in, lb));
+      case 10: return f(PfspFrontProblem<10, 500>(in, lb));
+      default: return f(PfspFrontProblem<20, 500>(in, lb));
     }
   }
   return with_pfsp_bucket(in.jobs, [&](auto nj) -> decltype(auto) {

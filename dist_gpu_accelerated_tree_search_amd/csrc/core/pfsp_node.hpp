@@ -187,8 +187,14 @@ TTS_HD inline Mask mask_first(int n) {
 // NJ (job bucket of the front layout): 20 keeps the unscheduled set in 32 bits, 50 in
 // 64 (the set then starts at byte 8 and the fronts at byte 16), 100 in a JobSet of two
 // 64-bit words (the set at byte 16, the fronts at byte 32: 48 / 64 / 80 B for 5 / 10 / 20
-// machines, where the permutation node is 112 B). One pattern for all: depth in byte 0,
-// padding to sizeof(Mask), the set, the u16 fronts.
+// machines, where the permutation node is 112 B). One pattern for these three: depth in
+// byte 0, padding to sizeof(Mask), the set, the u16 fronts.
+// 200 and 500 (TTS_FRONT_WIDE=2) keep the set in a JobSet of four / eight words. Padding
+// the header to sizeof(Mask) would waste 31 / 63 bytes there, so these two have a 16-byte
+// header: the depth as a u16 in bytes 0-1 (it reaches 499), the rest zero; the set at byte
+// 16, low word first; the u16 fronts at byte 16 + 8 W:
+//   200 jobs   64 /  80 /  96 B for 5 / 10 / 20 machines (permutation node  208 B)
+//   500 jobs   96 / 112 / 128 B                          (permutation node 1008 B)
 template <int NJ>
 using PfspJobMask =
     std::conditional_t<(NJ <= 32), uint32_t, std::conditional_t<(NJ <= 64), uint64_t, JobSet<(NJ + 63) / 64>>>;
@@ -198,8 +204,10 @@ struct alignas(16) PfspFrontNode {
   static constexpr int kMachines = MB;
   static constexpr int kJobs = NJ;
   using Mask = PfspJobMask<NJ>;
-  uint8_t depth;
-  uint8_t pad[sizeof(Mask) - 1];
+  using depth_t = std::conditional_t<(NJ > 100), uint16_t, uint8_t>;
+  static constexpr int kHeader = NJ > 100 ? 16 : static_cast<int>(sizeof(Mask));  // bytes before the set
+  depth_t depth;
+  uint8_t pad[kHeader - sizeof(depth_t)];
   Mask rest;
   uint16_t front[MB];
 };
@@ -214,6 +222,20 @@ static_assert(sizeof(JobSet<2>) == 16 && sizeof(PfspFrontNode<5, 100>) == 48 && 
 using PfspFrontNodeWidest = PfspFrontNode<20, 100>;
 static_assert(__builtin_offsetof(PfspFrontNodeWidest, rest) == 16 && __builtin_offsetof(PfspFrontNodeWidest, front) == 32,
               "100-job front node: the set at byte 16, the fronts at byte 32");
+static_assert(sizeof(JobSet<4>) == 32 && sizeof(PfspFrontNode<5, 200>) == 64 && sizeof(PfspFrontNode<10, 200>) == 80 &&
+                  sizeof(PfspFrontNode<20, 200>) == 96,
+              "200-job front node sizes");
+static_assert(sizeof(JobSet<8>) == 64 && sizeof(PfspFrontNode<5, 500>) == 96 && sizeof(PfspFrontNode<10, 500>) == 112 &&
+                  sizeof(PfspFrontNode<20, 500>) == 128,
+              "500-job front node sizes");
+using PfspFrontNode200 = PfspFrontNode<20, 200>;
+using PfspFrontNode500 = PfspFrontNode<20, 500>;
+static_assert(sizeof(PfspFrontNode200::depth_t) == 2 && __builtin_offsetof(PfspFrontNode200, depth) == 0 &&
+                  __builtin_offsetof(PfspFrontNode200, rest) == 16 && __builtin_offsetof(PfspFrontNode200, front) == 48,
+              "200-job front node: u16 depth, the set at byte 16, the fronts at byte 48");
+static_assert(sizeof(PfspFrontNode500::depth_t) == 2 && __builtin_offsetof(PfspFrontNode500, depth) == 0 &&
+                  __builtin_offsetof(PfspFrontNode500, rest) == 16 && __builtin_offsetof(PfspFrontNode500, front) == 80,
+              "500-job front node: u16 depth, the set at byte 16, the fronts at byte 80");
 
 // Job-count buckets a run-time instance is dispatched to.
 inline int pfsp_bucket(int jobs) {

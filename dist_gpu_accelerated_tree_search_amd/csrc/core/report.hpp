@@ -23,6 +23,7 @@ struct PfspArgs {
   int inst = 14, lb = 1, ub = 1, m = 25, M = 50000, T = 5000, D = 1, C = 1, ws = 1, L = 1;
   double perc = 0.5;
   bool front_wide = false;  // --front-wide: front nodes for 51-100 jobs too (TTS_FRONT_WIDE=1)
+  bool front_all = false;   // --front-all: front nodes for 51-500 jobs (TTS_FRONT_WIDE=2)
 };
 
 inline PfspArgs parse_pfsp_args(int argc, char* argv[]) {
@@ -33,6 +34,7 @@ inline PfspArgs parse_pfsp_args(int argc, char* argv[]) {
                                          {"D", required_argument, nullptr, 'D'},    {"C", required_argument, nullptr, 'C'},
                                          {"ws", required_argument, nullptr, 'w'},   {"L", required_argument, nullptr, 'L'},
                                          {"perc", required_argument, nullptr, 'p'}, {"front-wide", no_argument, nullptr, 'F'},
+                                         {"front-all", no_argument, nullptr, 'A'},
                                          {nullptr, 0, nullptr, 0}};
   int opt, idx = 0;
   auto fail = [](const char* msg) {
@@ -55,11 +57,12 @@ inline PfspArgs parse_pfsp_args(int argc, char* argv[]) {
       case 'L': if (v < 0 || v > 1) fail("Error: unsupported distributed dynamic load balancing option"); a.L = v; break;
       case 'p': if (v <= 0 || v > 100) fail("Error: unsupported WS percentage for popFrontBulkFree"); a.perc = v / 100.0; break;
       // set here, before any engine or rank exists: pfsp_front_ok reads it (core/pfsp_front.hpp)
-      case 'F': a.front_wide = true; setenv("TTS_FRONT_WIDE", "1", 1); break;
+      case 'F': a.front_wide = true; if (!a.front_all) setenv("TTS_FRONT_WIDE", "1", 1); break;
+      case 'A': a.front_all = true; setenv("TTS_FRONT_WIDE", "2", 1); break;
       default:
         std::fprintf(stderr,
                      "Usage: %s --inst <value> --lb <value> --ub <value> --m <value> --M <value> --T <value> --D <value> "
-                     "--C <value> --w <value> --L <value> --perc <value> [--front-wide]\n",
+                     "--C <value> --w <value> --L <value> --perc <value> [--front-wide] [--front-all]\n",
                      argv[0]);
         std::exit(EXIT_FAILURE);
     }

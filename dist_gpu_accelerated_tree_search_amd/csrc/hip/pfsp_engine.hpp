@@ -341,7 +341,7 @@ std::vector<int> pfsp_expand_probe(const PfspInstance& in, int lb, const void* p
                                    int variant, int reps = 0, std::vector<double>* timing = nullptr,
                                    ExpandProbeResult* extra = nullptr);
 ExpandProbeResult pfsp_lb1_expand_probe(const PfspInstance& in, const void* parents, size_t n, int best, int device);
-// front-layout instances only (pfsp_front_ok): the 20-, 50- and 100-job front buckets
+// front-layout instances only (pfsp_front_ok): the 20- to 500-job front buckets
 std::vector<double> pfsp_front_time(const PfspInstance& in, int lb, const void* nodes, size_t n, int best,
                                     const EngineConfig& cfg, int reps);
 FrontProbeResult pfsp_front_probe(const PfspInstance& in, int lb, const void* nodes, size_t n, int best,
@@ -375,6 +375,8 @@ TTS_PFSP_DECLARE_BUCKET(500)
 TTS_PFSP_DECLARE_FRONT_BUCKET(20)
 TTS_PFSP_DECLARE_FRONT_BUCKET(50)
 TTS_PFSP_DECLARE_FRONT_BUCKET(100)
+TTS_PFSP_DECLARE_FRONT_BUCKET(200)
+TTS_PFSP_DECLARE_FRONT_BUCKET(500)
 
 // Body of one bucket's TU: machine buckets (with_machine_bucket), LB kernels 1 (LB1
 // and LB1_d) / 2.
@@ -382,7 +384,7 @@ TTS_PFSP_DECLARE_FRONT_BUCKET(100)
   std::unique_ptr<IEngine> make_pfsp_engine_nj##NJ(const PfspInstance& in, int lb, const EngineConfig& cfg) { \
     return with_machine_bucket(in.machines, [&](auto mm) -> std::unique_ptr<IEngine> {               \
       constexpr int M = decltype(mm)::value;                                                         \
-      if constexpr (NJ == 20 || NJ == 50 || NJ == 100)                                               \
+      /* (every job bucket has a front layout: 200 and 500 under TTS_FRONT_WIDE=2) */                \
         if (pfsp_front_ok(in, lb)) return make_pfsp_front_engine_t<M, NJ>(in, cfg);                  \
       if (lb != 2) return make_pfsp_engine_t<NJ, M, 1>(in, cfg);                                    \
       if (M >= 10 && lb2_pk_wanted(in)) return make_pfsp_engine_t<NJ, M, 5>(in, cfg);                 \
@@ -393,7 +395,7 @@ TTS_PFSP_DECLARE_FRONT_BUCKET(100)
                                           int device) {                                              \
     return with_machine_bucket(in.machines, [&](auto mm) {                                           \
       constexpr int M = decltype(mm)::value;                                                         \
-      if constexpr (NJ == 20 || NJ == 50 || NJ == 100)                                               \
+      /* (every job bucket has a front layout: 200 and 500 under TTS_FRONT_WIDE=2) */                \
         if (pfsp_front_ok(in, lb))                                                                   \
           return pfsp_front_bounds_t<M, NJ>(in, static_cast<const PfspNode<NJ>*>(parents), n, device); \
       return lb == 2 ? pfsp_gpu_bounds_t<NJ, M, 2>(in, parents, n, best, device)                    \
@@ -417,7 +419,7 @@ TTS_PFSP_DECLARE_FRONT_BUCKET(100)
     });                                                                                              \
   }
 
-// The front probes of one front bucket (20, 50 or 100 jobs), after TTS_PFSP_DEFINE_BUCKET
+// The front probes of one front bucket (20 to 500 jobs), after TTS_PFSP_DEFINE_BUCKET
 // in its TU.
 #define TTS_PFSP_DEFINE_FRONT_BUCKET(NJ)                                                               \
   FrontProbeResult pfsp_front_probe_nj##NJ(const PfspInstance& in, int lb, const void* nodes, size_t n, int best, \

@@ -44,11 +44,13 @@ ExpandProbeResult pfsp_lb1_expand_probe(const PfspInstance& in, const void* pare
   }
 }
 
-// The front probes: the front buckets of 20, 50 and 100 jobs.
+// The front probes: the front buckets of 20, 50, 100, 200 and 500 jobs.
 FrontProbeResult pfsp_front_probe(const PfspInstance& in, int lb, const void* nodes, size_t n, int best,
                                   const EngineConfig& cfg, unsigned cap, int split_rank, int split_world,
                                   size_t split_min) {
   if (!pfsp_front_ok(in, lb)) throw std::invalid_argument("front probe: the front layout does not apply");
+  if (in.jobs > 200) return pfsp_front_probe_nj500(in, lb, nodes, n, best, cfg, cap, split_rank, split_world, split_min);
+  if (in.jobs > 100) return pfsp_front_probe_nj200(in, lb, nodes, n, best, cfg, cap, split_rank, split_world, split_min);
   if (in.jobs > 50) return pfsp_front_probe_nj100(in, lb, nodes, n, best, cfg, cap, split_rank, split_world, split_min);
   if (in.jobs > 20) return pfsp_front_probe_nj50(in, lb, nodes, n, best, cfg, cap, split_rank, split_world, split_min);
   return pfsp_front_probe_nj20(in, lb, nodes, n, best, cfg, cap, split_rank, split_world, split_min);
@@ -57,6 +59,8 @@ FrontProbeResult pfsp_front_probe(const PfspInstance& in, int lb, const void* no
 std::vector<double> pfsp_front_time(const PfspInstance& in, int lb, const void* nodes, size_t n, int best,
                                     const EngineConfig& cfg, int reps) {
   if (!pfsp_front_ok(in, lb)) throw std::invalid_argument("front timing: the front layout does not apply");
+  if (in.jobs > 200) return pfsp_front_time_nj500(in, lb, nodes, n, best, cfg, reps);
+  if (in.jobs > 100) return pfsp_front_time_nj200(in, lb, nodes, n, best, cfg, reps);
   if (in.jobs > 50) return pfsp_front_time_nj100(in, lb, nodes, n, best, cfg, reps);
   if (in.jobs > 20) return pfsp_front_time_nj50(in, lb, nodes, n, best, cfg, reps);
   return pfsp_front_time_nj20(in, lb, nodes, n, best, cfg, reps);
@@ -65,6 +69,8 @@ std::vector<double> pfsp_front_time(const PfspInstance& in, int lb, const void* 
 FrontExpandResult pfsp_front_expand_probe(const PfspInstance& in, int lb, const void* nodes, size_t n, int best, int steps,
                                           int device, bool production) {
   if (!pfsp_front_ok(in, lb)) throw std::invalid_argument("front expand probe: the front layout does not apply");
+  if (in.jobs > 200) return pfsp_front_expand_probe_nj500(in, nodes, n, best, steps, device, production);
+  if (in.jobs > 100) return pfsp_front_expand_probe_nj200(in, nodes, n, best, steps, device, production);
   if (in.jobs > 50) return pfsp_front_expand_probe_nj100(in, nodes, n, best, steps, device, production);
   if (in.jobs > 20) return pfsp_front_expand_probe_nj50(in, nodes, n, best, steps, device, production);
   return pfsp_front_expand_probe_nj20(in, nodes, n, best, steps, device, production);

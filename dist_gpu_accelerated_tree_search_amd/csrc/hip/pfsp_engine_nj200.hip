@@ -4,4 +4,6 @@
 
 namespace tts {
 TTS_PFSP_DEFINE_BUCKET(200)
+// 101-200 jobs on front nodes with 256-bit job sets (TTS_FRONT_WIDE=2)
+TTS_PFSP_DEFINE_FRONT_BUCKET(200)
 }  // namespace tts

@@ -4,4 +4,6 @@
 
 namespace tts {
 TTS_PFSP_DEFINE_BUCKET(500)
+// 201-500 jobs on front nodes with 512-bit job sets (TTS_FRONT_WIDE=2)
+TTS_PFSP_DEFINE_FRONT_BUCKET(500)
 }  // namespace tts

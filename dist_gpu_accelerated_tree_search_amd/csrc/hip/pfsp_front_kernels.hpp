@@ -35,11 +35,15 @@ namespace dev {
 
 template <int M, int NJ_ = 20>
 struct FrontGeom {
-  static constexpr int NJ = NJ_;                        // children per parent at most (job bucket 20, 50 or 100)
+  static constexpr int NJ = NJ_;                        // children per parent at most (job bucket 20 to 500)
   using Node = PfspFrontNode<M, NJ>;
-  using Mask = typename Node::Mask;                     // unscheduled-job set: 32, 64 or 128 bits (JobSet<2>)
-  static constexpr int MO = sizeof(Mask) / 4;           // first word of the set (1, 2 or 4) = its 32-bit words
-  static constexpr int FO = 2 * MO;                     // first word of the fronts (2, 4 or 8)
+  using Mask = typename Node::Mask;                     // unscheduled-job set: 32, 64 or 64 W bits (JobSet<W>)
+  static constexpr int SW = sizeof(Mask) / 4;           // 32-bit words of the set (1, 2, 4, 8 or 16)
+  static constexpr int MO = Node::kHeader / 4;          // first word of the set (1, 2 or 4: the header's words)
+  static constexpr int FO = MO + SW;                    // first word of the fronts (2, 4, 8, 12 or 20)
+  static_assert(MO * 4 == __builtin_offsetof(Node, rest) && FO * 4 == __builtin_offsetof(Node, front), "node words");
+  // the depth in word 0: a byte up to 100 jobs, a u16 above (it reaches 499)
+  static constexpr uint32_t DMASK = NJ > 100 ? 0xffffu : 0xffu;
   static constexpr int NW = sizeof(Node) / 4;           // node words in registers (8 to 20)
   static constexpr int VPN = sizeof(Node) / 16;         // 16-B vectors per node
   static constexpr int BP = 256;                        // parents per chunk: one per thread
@@ -52,7 +56,8 @@ struct FrontGeom {
   // local chunk, LMAX * 2 * CAP in a multi-level one, never by MAXCH)
   static_assert(LT * BP < 65536, "the halves of the leaf word count expanded nodes");
   // bits of the survivor count in the one-level kernel's combined scan (leaves above them)
-  static constexpr int SB = NJ <= 20 ? 13 : 15;
+  // (256 x 199 = 50,944 and 256 x 499 = 127,744 above 100 jobs: 17 bits)
+  static constexpr int SB = NJ <= 20 ? 13 : NJ <= 100 ? 15 : 17;
   static_assert(BP * (NJ - 1) < (1 << SB) && SB + 9 < 31, "survivors of a chunk and its leaves (<= 256) share one scan word");
   static constexpr int MAXCHUNKS = 2048;
   // multi-level chunks (front_multi_level): up to BPF_CP parents, spread over the grid
@@ -78,14 +83,21 @@ struct FrontGeom {
   // (100-job nodes, 12 / 16 / 20 words and a four-word set: 5 / 4 / 3, which is also what a
   // CU's 160 KB of LDS holds of FrontSmem<M, 100>; 0 B scratch at these budgets,
   // profiles/r9/kernel_resources.md)
-  static constexpr int WAVES = NJ > 50   ? (M <= 5 ? 5 : M <= 10 ? 4 : 3)
+  // (200- and 500-job nodes, 16 to 32 words and a set of 8 / 16 words: the budgets that keep
+  // the production kernels at 0 B scratch and within what a CU's LDS holds of
+  // FrontSmem<M, 200 / 500>, profiles/r11/kernel_resources.md)
+  static constexpr int WAVES = NJ > 200   ? (M <= 5 ? 3 : 2)
+                               : NJ > 100 ? (M <= 5 ? 4 : 3)
+                               : NJ > 50  ? (M <= 5 ? 5 : M <= 10 ? 4 : 3)
                                : NJ > 20 ? (M <= 5 ? 6 : M <= 10 ? 5 : 4)
                                          : (M <= 10 ? 6 : 4);
   // resident workgroups per CU the engine's grid is sized for: under the step priority one
   // below the register budget's 6 for 20-job, <= 10-machine instances (ta014 0.1840 ->
   // 0.1822 ms, 2/4/8-way shares -2..-4 %, ta008 3 engines +8 %; profiles/r5/grid_ab.txt)
   static constexpr int GRID_WGS = NJ > 20 ? WAVES : (M <= 10 ? 5 : 4);
-  // probe records (tests): {job | kind << 8, lb, parent words, parent remain}
+  // probe records (tests): {job | kind << KS, lb, parent words, parent remain}; the kind
+  // above a byte of job id up to 100 jobs, above 16 bits in the 200- and 500-job buckets
+  static constexpr int KS = NJ > 100 ? 16 : 8;
   static constexpr int DBGW = (2 + NW + (M + 1) / 2 + 3) / 4 * 4;
   static constexpr int HW = (M + 1) / 2;  // packed u16 pairs of a p row / a remain
   // u16 row stride of the LDS p table (as PfspConsts::MS): 16 B for M <= 8, else 48 B
@@ -97,6 +109,10 @@ struct FrontGeom {
   // (profiles/r7/kernel_resources.md), and ta021 did not move (9.43 against 9.49 s, inside
   // the spread: profiles/r7/full_and_regress.txt; A/B builds: -DTTS_EMIT_BALANCED_MAXM=20)
   static constexpr int DW = 256;
+  // a descriptor is owner lane << DS | job in 16 bits: 6 lane bits above 8 job bits, above 9
+  // in the 500-job bucket
+  static constexpr int DS = NJ > 256 ? 9 : 8;
+  static_assert(NJ <= (1 << DS) && DS + 6 <= 16, "a descriptor holds a lane and a job");
   static constexpr bool BAL = M <= TTS_EMIT_BALANCED_MAXM;
   // dynamic local DFS (front_dyn): the 20- and 50-job buckets only
   static constexpr bool DYN = NJ <= 50;
@@ -191,7 +207,7 @@ struct FrontSmem {
     };
   };
   PoolSmem<G::MAXCHUNKS> pool;
-  // wave-balanced emit: each wave's survivor descriptors, owner lane << 8 | job
+  // wave-balanced emit: each wave's survivor descriptors, owner lane << DS | job
   // (front_emit_balanced; a wave touches its own row only)
   uint16_t desc[kBlock / kWave][G::BAL ? G::DW : 1];
 };
@@ -199,6 +215,13 @@ static_assert(FrontGeom<5, 100>::GRID_WGS * sizeof(FrontSmem<5, 100>) <= 160 * 1
                   FrontGeom<10, 100>::GRID_WGS * sizeof(FrontSmem<10, 100>) <= 160 * 1024 &&
                   FrontGeom<20, 100>::GRID_WGS * sizeof(FrontSmem<20, 100>) <= 160 * 1024,
               "the 100-job grids' resident workgroups fit a CU's LDS");
+static_assert(FrontGeom<5, 200>::GRID_WGS * sizeof(FrontSmem<5, 200>) <= 160 * 1024 &&
+                  FrontGeom<10, 200>::GRID_WGS * sizeof(FrontSmem<10, 200>) <= 160 * 1024 &&
+                  FrontGeom<20, 200>::GRID_WGS * sizeof(FrontSmem<20, 200>) <= 160 * 1024 &&
+                  FrontGeom<5, 500>::GRID_WGS * sizeof(FrontSmem<5, 500>) <= 160 * 1024 &&
+                  FrontGeom<10, 500>::GRID_WGS * sizeof(FrontSmem<10, 500>) <= 160 * 1024 &&
+                  FrontGeom<20, 500>::GRID_WGS * sizeof(FrontSmem<20, 500>) <= 160 * 1024,
+              "the 200- and 500-job grids' resident workgroups fit a CU's LDS");
 
 template <int M, int NJ>
 __device__ inline void front_row(const uint16_t* row, int (&pr)[M]) {
@@ -219,18 +242,19 @@ __device__ inline int front_of(const uint32_t (&w)[FrontGeom<M, NJ>::NW], int m)
 }
 
 // The unscheduled-job set of the node held in w (word 1, words 2-3 for 50 jobs, words 4-7
-// for 100).
+// for 100, 4-11 for 200, 4-19 for 500).
 template <int M, int NJ>
 __device__ inline typename FrontGeom<M, NJ>::Mask front_mask(const uint32_t (&w)[FrontGeom<M, NJ>::NW]) {
   constexpr int MO = FrontGeom<M, NJ>::MO;
-  if constexpr (MO == 1) {
+  if constexpr (FrontGeom<M, NJ>::SW == 1) {
     return w[1];
-  } else if constexpr (MO == 2) {
+  } else if constexpr (FrontGeom<M, NJ>::SW == 2) {
     return static_cast<u64>(w[2]) | (static_cast<u64>(w[3]) << 32);
   } else {
     typename FrontGeom<M, NJ>::Mask x;
 #pragma unroll
-    for (int k = 0; k < MO / 2; ++k) x.w[k] = static_cast<u64>(w[MO + 2 * k]) | (static_cast<u64>(w[MO + 2 * k + 1]) << 32);
+    for (int k = 0; k < FrontGeom<M, NJ>::SW / 2; ++k)
+      x.w[k] = static_cast<u64>(w[MO + 2 * k]) | (static_cast<u64>(w[MO + 2 * k + 1]) << 32);
     return x;
   }
 }
@@ -238,14 +262,14 @@ __device__ inline typename FrontGeom<M, NJ>::Mask front_mask(const uint32_t (&w)
 template <int M, int NJ>
 __device__ inline void front_mask_put(const typename FrontGeom<M, NJ>::Mask& x, uint32_t (&c)[FrontGeom<M, NJ>::NW]) {
   constexpr int MO = FrontGeom<M, NJ>::MO;
-  if constexpr (MO == 1) {
+  if constexpr (FrontGeom<M, NJ>::SW == 1) {
     c[1] = x;
-  } else if constexpr (MO == 2) {
+  } else if constexpr (FrontGeom<M, NJ>::SW == 2) {
     c[2] = static_cast<uint32_t>(x);
     c[3] = static_cast<uint32_t>(static_cast<u64>(x) >> 32);
   } else {
 #pragma unroll
-    for (int k = 0; k < MO / 2; ++k) {
+    for (int k = 0; k < FrontGeom<M, NJ>::SW / 2; ++k) {
       c[MO + 2 * k] = static_cast<uint32_t>(x.w[k]);
       c[MO + 2 * k + 1] = static_cast<uint32_t>(x.w[k] >> 32);
     }
@@ -255,7 +279,9 @@ __device__ inline void front_mask_put(const typename FrontGeom<M, NJ>::Mask& x, 
 // f(x, base) for each machine word x of a job set in turn, base the job of its bit 0: the
 // loops over a set's jobs run one 64-bit word at a time (`for (; x; x &= x - 1)` on x,
 // job base + mask_ctz(x)), ascending. A one-word set is its own word. The words of a wider
-// set are picked by comparison in a loop that stays rolled: one copy of the body.
+// set are picked by comparison in a loop that stays rolled: one copy of the body. (Picking
+// word k costs W and-or steps on a uniform k, 8 per word at W = 8, against a body of an O(M)
+// chain per job of the word.)
 template <class F>
 __device__ inline void mask_words(uint32_t x, F&& f) { f(x, 0); }
 template <class F>
@@ -264,9 +290,17 @@ template <int W, class F>
 __device__ inline void mask_words(const JobSet<W>& s, F&& f) {
 #pragma unroll 1
   for (int k = 0; k < W; ++k) {
-    uint64_t x = s.w[0];
+    uint64_t x = 0;
+    if constexpr (W <= 2) {
+      x = s.w[0];
 #pragma unroll
-    for (int i = 1; i < W; ++i) x = k == i ? s.w[i] : x;
+      for (int i = 1; i < W; ++i) x = k == i ? s.w[i] : x;
+    } else {
+      // (four and eight words: a chain of selects on k is folded into w[k], an indexed read
+      // of a set the compiler then keeps in scratch; and-or with a per-word mask is not)
+#pragma unroll
+      for (int i = 0; i < W; ++i) x |= s.w[i] & (k == i ? ~uint64_t(0) : uint64_t(0));
+    }
     f(x, 64 * k);
   }
 }
@@ -301,7 +335,7 @@ __device__ inline void front_dbg(const PfspFrontArgs<M, NJ>& a, int kind, const 
   const unsigned i = atomicAdd(a.dbg_n, 1u);
   if (i >= a.dbg_cap) return;
   uint32_t* r = a.dbg_rec + static_cast<size_t>(i) * G::DBGW;
-  r[0] = static_cast<uint32_t>(j) | (static_cast<uint32_t>(kind) << 8);
+  r[0] = static_cast<uint32_t>(j) | (static_cast<uint32_t>(kind) << G::KS);
   r[1] = static_cast<uint32_t>(lb);
 #pragma unroll
   for (int k = 0; k < G::NW; ++k) r[2 + k] = w[k];
@@ -466,7 +500,7 @@ template <int M, int NJ>
 __device__ inline void front_child(const FrontSmem<M, NJ>& sm, const uint32_t (&w)[FrontGeom<M, NJ>::NW], int j,
                                    uint32_t (&c)[FrontGeom<M, NJ>::NW]) {
   constexpr int NW = FrontGeom<M, NJ>::NW;
-  const int d = static_cast<int>(w[0] & 0xffu);
+  const int d = static_cast<int>(w[0] & FrontGeom<M, NJ>::DMASK);
   const bool root = d == 0;
   int pr[M];
   front_row<M, NJ>(sm.ptab[j], pr);
@@ -525,7 +559,7 @@ __device__ inline void front_emit(const FrontSmem<M, NJ>& sm, const uint32_t (&w
 // 1.1 - 2.8 rounds of 64, scripts/emit_imbalance.py). Output positions are those of the
 // per-lane loop: the k-th survivor (ascending job) of a lane whose exclusive scan offset
 // is off goes to store(off + k, child words, child remain).
-//   1. every lane lists its survivors as descriptors (owner lane << 8 | job) in its
+//   1. every lane lists its survivors as descriptors (owner lane << DS | job) in its
 //      wave's LDS row, at its wave-local offset (off minus lane 0's): a short divergent
 //      walk, no chain;
 //   2. round r: lane i takes descriptor 64 r + i, fetches the owner's node words (and
@@ -553,7 +587,7 @@ __device__ inline void front_emit_balanced(FrontSmem<M, NJ>& sm, const uint32_t 
       __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
       __builtin_amdgcn_wave_barrier();
       for (; !mask_empty(surv) && pos < s0 + DW; ++pos) {
-        desc[pos & (DW - 1)] = static_cast<uint16_t>((lane << 8) | mask_ctz(surv));
+        desc[pos & (DW - 1)] = static_cast<uint16_t>((lane << G::DS) | mask_ctz(surv));
         mask_pop_low(surv);
       }
       __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -562,8 +596,8 @@ __device__ inline void front_emit_balanced(FrontSmem<M, NJ>& sm, const uint32_t 
     }
     const int s = s0 + lane;
     const uint32_t d = desc[min(s, S - 1) & (DW - 1)];
-    const int j = static_cast<int>(d & 0xffu);
-    const int src4 = static_cast<int>(d >> 8) << 2;
+    const int j = static_cast<int>(d & ((1u << G::DS) - 1u));
+    const int src4 = static_cast<int>(d >> G::DS) << 2;
     uint32_t pw[NW], pr[HW];
 #pragma unroll
     for (int i = 0; i < NW; ++i) {
@@ -644,10 +678,14 @@ __device__ inline int front_child_offsets(FrontSmem<M, NJ>& sm, const uint4 (*sr
   int T = 0;
   int k = 0;
   if (static_cast<int>(threadIdx.x) < n) {
-    // the set: word 1 (20 jobs) or words 2-3 (50 jobs) of vector 0, all of vector 1 (100 jobs)
+    // the set: word 1 (20 jobs) or words 2-3 (50 jobs) of vector 0, all of vector 1 (100
+    // jobs), of vectors 1-2 (200 jobs) or 1-4 (500 jobs)
     if constexpr (FrontGeom<M, NJ>::MO == 4) {
-      const uint4 h = src[threadIdx.x][1];
-      k = __popc(h.x) + __popc(h.y) + __popc(h.z) + __popc(h.w);
+#pragma unroll
+      for (int q = 0; q < FrontGeom<M, NJ>::SW / 4; ++q) {
+        const uint4 h = src[threadIdx.x][1 + q];
+        k += __popc(h.x) + __popc(h.y) + __popc(h.z) + __popc(h.w);
+      }
     } else {
       const uint4 h = src[threadIdx.x][0];
       k = FrontGeom<M, NJ>::MO == 1 ? __popc(h.y) : __popc(h.z) + __popc(h.w);
@@ -721,7 +759,7 @@ __device__ inline int front_expand_cp(const A& a, FrontSmem<M, NJ>& sm, const ui
       }
       if (front_rec(a)) front_dbg<M, NJ>(a, kind, w, rp, j, lb);
       const bool kp = keep(lo, j);
-      if (static_cast<int>(w[0] & 0xffu) + 1 == a.jobs) {
+      if (static_cast<int>(w[0] & FrontGeom<M, NJ>::DMASK) + 1 == a.jobs) {
         nleaf += kp;
         if (lb < best) atomicMin(&a.pool.ctl->best.v, lb);
       } else {
@@ -755,7 +793,7 @@ __device__ inline int front_expand_tp_regs(const A& a, FrontSmem<M, NJ>& sm,
   constexpr int HW = G::HW;
   typename G::Mask surv{};
   int nsurv = 0;
-  const bool leaf = static_cast<int>(w[0] & 0xffu) + 1 == a.jobs;
+  const bool leaf = static_cast<int>(w[0] & FrontGeom<M, NJ>::DMASK) + 1 == a.jobs;
   {
     uint32_t fb[M], rb[M];
     front_broadcast<M, NJ>(a, w, rp, fb, rb);
@@ -1014,7 +1052,7 @@ __device__ inline void front_local(const A& a, FrontSmem<M, NJ>& sm, const IterV
       }
       typename G::Mask surv{};
       int nsurv = 0;
-      const bool leaf = static_cast<int>(w[0] & 0xffu) + 1 == a.jobs;
+      const bool leaf = static_cast<int>(w[0] & FrontGeom<M, NJ>::DMASK) + 1 == a.jobs;
       if (!have_r) front_remain<M, NJ>(sm, w, rp);
       front_parent_r<M, NJ>(
           a, sm, w, rp,
@@ -1285,7 +1323,7 @@ __device__ inline void front_dyn(const PfspFrontArgs<M, NJ>& a, FrontSmem<M, NJ>
                                            __HIP_MEMORY_SCOPE_AGENT);
     typename G::Mask surv = 0;
     int nsurv = 0;
-    const bool leaf = static_cast<int>(w[0] & 0xffu) + 1 == a.jobs;
+    const bool leaf = static_cast<int>(w[0] & FrontGeom<M, NJ>::DMASK) + 1 == a.jobs;
     if (!have_r) front_remain<M, NJ>(sm, w, rp);
     front_parent_r<M, NJ>(
         a, sm, w, rp,
@@ -1559,7 +1597,7 @@ void pfsp_front_kernel(FrontArgsT<M, NJ, INSTR> a, int t) {
     for (int i = 0; i < G::NW; ++i) w[i] = 0;
     if (gi < v.B) front_load<M, NJ>(pool_parent<Node, G::SLOT, G::MAXCHUNKS>(pa, v, t, gi, sm.pool), w);
     const bool first = ch == static_cast<int>(blockIdx.x);
-    const bool leaf = static_cast<int>(w[0] & 0xffu) + 1 == a.jobs;
+    const bool leaf = static_cast<int>(w[0] & FrontGeom<M, NJ>::DMASK) + 1 == a.jobs;
     // children this rank keeps (all of them outside the split iteration)
     using Mask = typename G::Mask;
     Mask kmask = mask_first<Mask>(8 * sizeof(Mask));

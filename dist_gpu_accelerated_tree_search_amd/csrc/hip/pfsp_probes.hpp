@@ -232,7 +232,8 @@ FrontProbeResult pfsp_front_probe_t(const PfspInstance& in, int lb, const void* 
   }
   for (size_t i = 0; i < res.checked; ++i) {
     const uint32_t* r = &rec[i * G::DBGW];
-    const int j = static_cast<int>(r[0] & 0xffu), kind = static_cast<int>((r[0] >> 8) & 0xffu);
+    // (job | kind << KS: the kind above 8 job bits up to 100 jobs, above 16 in the wider buckets)
+    const int j = static_cast<int>(r[0] & ((1u << G::KS) - 1u)), kind = static_cast<int>((r[0] >> G::KS) & 0xffu);
     if (kind < 6) ++res.by_kind[kind];
     Node parent;
     std::memcpy(&parent, r + 2, sizeof(Node));

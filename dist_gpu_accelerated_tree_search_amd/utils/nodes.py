@@ -6,7 +6,10 @@ id_t = uint8 for NJ <= 255 else uint16. PFSP front node (LB1 / LB1_d engines on 
 7 pad and a uint64 mask; 51-100 jobs, with TTS_FRONT_WIDE=1: 15 pad and a 128-bit mask of
 two uint64 words, low word first), padded
 to 16 B (32 B for MB <= 10 machines, 48 B for 20; 50 jobs: 32 / 48 / 64 B and 100 jobs:
-48 / 64 / 80 B for 5 / 10 / 20 machines). N-Queens node: 4 x uint32
+48 / 64 / 80 B for 5 / 10 / 20 machines). 101-500 jobs, with TTS_FRONT_WIDE=2: a 16-byte
+header (uint16 depth, 14 zero bytes), a mask of 4 (up to 200 jobs) or 8 uint64 words at byte
+16, low word first, then the fronts (200 jobs: 64 / 80 / 96 B, 500 jobs: 96 / 112 / 128 B).
+N-Queens node: 4 x uint32
 {cols, diag, anti, depth}. Parity: ref pfsp/lib/PFSP_node.h:15-20 (44-B node with
 limit1 stored), nqueens/lib/NQueens_node.h:13-17 (board).
 """
@@ -66,10 +69,16 @@ def pfsp_front_unpack(nodes: np.ndarray, machines_bucket: int, jobs: int = 20):
     50 jobs it is 64 bits at byte 8 and the fronts start at byte 16; up to 100 jobs it is
     128 bits at byte 16 (two uint64 words, low word first) and the fronts start at byte 32:
     the masks then come back as an object array of Python ints, and pfsp_front_set_words
-    gives the two uint64 columns."""
+    gives the two uint64 columns. Up to 200 / 500 jobs the depth is a uint16 in bytes 0-1,
+    the set 4 / 8 uint64 words at byte 16 and the fronts start at byte 48 / 80."""
     a = np.ascontiguousarray(nodes, dtype=np.uint8)
     depths = a[:, 0].astype(np.int64)
-    if jobs <= 20:
+    if jobs > 100:
+        depths = a[:, 0:2].copy().view(np.uint16).reshape(-1).astype(np.int64)
+        w = pfsp_front_set_words(a, jobs)
+        rest = np.array([sum(int(x) << (64 * k) for k, x in enumerate(row)) for row in w], dtype=object)
+        f0 = 16 + 8 * w.shape[1]
+    elif jobs <= 20:
         rest = a[:, 4:8].copy().view(np.uint32).reshape(-1).astype(np.int64)
         f0 = 8
     elif jobs > 50:
@@ -83,11 +92,13 @@ def pfsp_front_unpack(nodes: np.ndarray, machines_bucket: int, jobs: int = 20):
     return depths, rest, fronts
 
 
-def pfsp_front_set_words(nodes: np.ndarray) -> np.ndarray:
-    """The 128-bit unscheduled sets of 51-100-job front nodes as (n, 2) uint64 words, low
-    word first (bit j of the set: bit j % 64 of word j // 64)."""
+def pfsp_front_set_words(nodes: np.ndarray, jobs: int = 100) -> np.ndarray:
+    """The unscheduled sets of front nodes above 50 jobs as (n, W) uint64 words, low word
+    first (bit j of the set: bit j % 64 of word j // 64): W = 2 for 51-100 jobs, 4 for
+    101-200, 8 for 201-500."""
     a = np.ascontiguousarray(nodes, dtype=np.uint8)
-    return a[:, 16:32].copy().view(np.uint64).reshape(-1, 2)
+    w = 2 if jobs <= 100 else 4 if jobs <= 200 else 8
+    return a[:, 16:16 + 8 * w].copy().view(np.uint64).reshape(-1, w)
 
 
 QUEENS_NODE_BYTES = 16
