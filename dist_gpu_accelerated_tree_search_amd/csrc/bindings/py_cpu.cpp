@@ -136,6 +136,21 @@ PYBIND11_MODULE(_tts_cpu, m) {
   });
   m.def("pfsp_front_layout", [](const PfspInstance& in, int lb) { return pfsp_front_ok(in, lb); });
   m.def(
+      "pfsp_front_remain_table",
+      [](const PfspInstance& in) {
+        const int mb = pfsp_machine_bucket(in.machines);
+        if (!pfsp_front_ok(in, 1) || pfsp_front_jobs(in.jobs) != 20 || mb == 0)
+          throw std::invalid_argument("pfsp_front_remain_table: 20-job front layout only");
+        const std::vector<uint32_t> t = pfsp_front_remain_table(in, mb);
+        py::array_t<uint32_t> out({static_cast<py::ssize_t>(kRemainGroups), static_cast<py::ssize_t>(kRemainPats),
+                                   static_cast<py::ssize_t>((mb + 1) / 2)});
+        std::memcpy(out.mutable_data(), t.data(), t.size() * sizeof(uint32_t));
+        return out;
+      },
+      py::arg("inst"),
+      "Remain table of a 20-job front instance, uint32 (groups, patterns, packed machine pairs): the remain of a "
+      "job set is the 32-bit sum of the rows [g][(set >> 4 g) & 15] (core/pfsp_front.hpp).");
+  m.def(
       "pool_deal",
       [](uint64_t B, uint64_t spread, uint64_t cap, bool wide) {
         if (spread == 0 || cap == 0) throw std::invalid_argument("pool_deal: spread and cap must be positive");

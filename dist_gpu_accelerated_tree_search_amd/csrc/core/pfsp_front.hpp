@@ -19,6 +19,7 @@
 #include <stdexcept>
 #include <type_traits>
 #include <utility>
+#include <vector>
 
 #include "pfsp_instance.hpp"
 #include "pfsp_node.hpp"
@@ -126,6 +127,33 @@ inline bool pfsp_front_ok(const PfspInstance& in, int lb) {
 // job bucket of the front layout: 20 (32-bit job sets), 50 (64-bit), 100 (128-bit), 200
 // (256-bit) or 500 (512-bit)
 inline int pfsp_front_jobs(int jobs) { return jobs <= 20 ? 20 : jobs <= 50 ? 50 : jobs <= 100 ? 100 : jobs <= 200 ? 200 : 500; }
+
+// Remain table of a 20-job front instance: the remain of a node (the sum of its unscheduled
+// jobs' p rows, per machine) depends on its job set and the instance only, so the 20-bit set
+// is cut into kRemainGroups groups of kRemainBits bits and the remain is the sum of one row
+// per group. Row [g][pat] holds, as packed u16 pairs (machine 2h in the low half of word h,
+// 2h + 1 in the high half, as a node's fronts), the p rows of the jobs kRemainBits g + b, b a set bit
+// of pat, summed. Jobs beyond the instance's and machines beyond it are zero. A machine's
+// column sum is below 65536 (pfsp_front_ok), so the 32-bit sum of the groups' rows never carries
+// from a low half into a high one. Built once per instance; the GPU front kernels stage the
+// same rows into LDS (csrc/hip/pfsp_front_kernels.hpp front_remain).
+// [kRemainGroups][kRemainPats][(MB + 1) / 2] packed words
+inline std::vector<uint32_t> pfsp_front_remain_table(const PfspInstance& in, int MB) {
+  if (in.jobs > 20 || in.machines > MB || MB > 20) throw std::invalid_argument("remain table: 20-job front buckets only");
+  const int HW = (MB + 1) / 2;
+  std::vector<uint32_t> t(static_cast<size_t>(kRemainGroups) * kRemainPats * HW, 0u);
+  for (int g = 0; g < kRemainGroups; ++g)
+    for (int pat = 1; pat < kRemainPats; ++pat) {
+      // the row of pat without its lowest bit, plus that bit's job
+      const int b = __builtin_ctz(static_cast<unsigned>(pat)), j = kRemainBits * g + b;
+      uint32_t* row = &t[(static_cast<size_t>(g) * kRemainPats + pat) * HW];
+      const uint32_t* prev = &t[(static_cast<size_t>(g) * kRemainPats + (pat & (pat - 1))) * HW];
+      for (int h = 0; h < HW; ++h) row[h] = prev[h];
+      if (j >= in.jobs) continue;
+      for (int m = 0; m < in.machines; ++m) row[m >> 1] += static_cast<uint32_t>(in.pt(m, j)) << ((m & 1) * 16);
+    }
+  return t;
+}
 
 template <int MB, int NJ = 20>
 struct PfspFrontProblem {

@@ -237,6 +237,14 @@ static_assert(sizeof(PfspFrontNode500::depth_t) == 2 && __builtin_offsetof(PfspF
                   __builtin_offsetof(PfspFrontNode500, rest) == 16 && __builtin_offsetof(PfspFrontNode500, front) == 80,
               "500-job front node: u16 depth, the set at byte 16, the fronts at byte 80");
 
+// Remain table of the 20-job front bucket (core/pfsp_front.hpp pfsp_front_remain_table): the
+// job set cut into kRemainGroups groups of kRemainBits bits, one table row per group pattern.
+// (Groups of 4 bits: 80 rows. Groups of 5 would save one row read per look-up with 128 rows,
+// 2,560 B for 10 machines, and that ends the sixth resident workgroup of the 10-machine front
+// kernel: 6 x 27,392 B against a CU's 163,840 B of LDS.)
+constexpr int kRemainBits = 4, kRemainGroups = 5, kRemainPats = 1 << kRemainBits;
+static_assert(kRemainBits * kRemainGroups == 20, "the groups cover a 20-job set");
+
 // Job-count buckets a run-time instance is dispatched to.
 inline int pfsp_bucket(int jobs) {
   if (jobs <= 20) return 20;

@@ -11,6 +11,7 @@
 
 #include <algorithm>
 #include <cstdlib>
+#include <cstring>
 #include <memory>
 #include <type_traits>
 #include <vector>
@@ -114,13 +115,32 @@ template <int M, int NJ>
 inline std::vector<uint16_t> pfsp_front_fill_args(const PfspInstance& in, dev::PfspFrontArgs<M, NJ>& a) {
   if (!pfsp_front_ok(in, 1) || pfsp_machine_bucket(in.machines) != M || pfsp_front_jobs(in.jobs) != NJ)
     throw std::invalid_argument("front layout does not apply to this instance");
-  constexpr int MS = dev::FrontGeom<M, NJ>::MS;
+  using G = dev::FrontGeom<M, NJ>;
+  constexpr int MS = G::MS;
   const PfspPadded t = pfsp_padded_tables(in, M);
-  std::vector<uint16_t> ptab(static_cast<size_t>(in.jobs) * MS, 0);
+  // (buckets with a remain table: all NJ rows, then the table as the kernels hold it in LDS, FrontRemTab:
+  // each 16-B vector of the rows as a column of its own, then the rows' remaining words)
+  std::vector<uint16_t> ptab(G::RTAB ? static_cast<size_t>(NJ) * MS + static_cast<size_t>(G::TVEC) * 8
+                                     : static_cast<size_t>(in.jobs) * MS,
+                             0);
   for (int j = 0; j < in.jobs; ++j)
     for (int m = 0; m < in.machines; ++m) ptab[static_cast<size_t>(j) * MS + m] = static_cast<uint16_t>(in.pt(m, j));
+  if constexpr (G::RTAB) {
+    const std::vector<uint32_t> rows = pfsp_front_remain_table(in, M);  // [row][HW]
+    std::vector<uint32_t> img(static_cast<size_t>(G::TVEC) * 4, 0u);
+    for (int r = 0; r < G::TROWS; ++r)
+      for (int h = 0; h < G::HW; ++h) {
+        const size_t at = h < 4 * G::TQ ? (static_cast<size_t>(h / 4) * G::TROWS + r) * 4 + h % 4
+                                        : static_cast<size_t>(G::TQ) * G::TROWS * 4 + static_cast<size_t>(r) * G::TR +
+                                              (h - 4 * G::TQ);
+        img[at] = rows[static_cast<size_t>(r) * G::HW + h];
+      }
+    std::memcpy(ptab.data() + static_cast<size_t>(NJ) * MS, img.data(), img.size() * sizeof(uint32_t));
+  }
   a.jobs = in.jobs;
   for (int m = 0; m < M; ++m) a.min_tails[m] = t.tails[m];
+  for (int h = 0; h < G::HW; ++h)
+    a.tails2[h] = static_cast<uint32_t>(t.tails[2 * h]) | (2 * h + 1 < M ? static_cast<uint32_t>(t.tails[2 * h + 1]) << 16 : 0u);
   a.bpf = dev::FrontGeom<M, NJ>::BPF;
   a.cp_max = dev::FrontGeom<M, NJ>::CPMAX;
   if (const char* f = std::getenv("TTS_CP_MAX")) a.cp_max = std::max(0, std::atoi(f));  // A/B runs

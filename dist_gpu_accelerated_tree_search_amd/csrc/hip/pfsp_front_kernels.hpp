@@ -103,6 +103,19 @@ struct FrontGeom {
   // u16 row stride of the LDS p table (as PfspConsts::MS): 16 B for M <= 8, else 48 B
   static constexpr int MS = M <= 8 ? 8 : 24;
   static constexpr int RV = (M + 7) / 8;                // 16-B vectors holding one row's M values
+  // remain table (20-job bucket, FrontRemTab): a row's HW packed words as TQ 16-B vectors and
+  // TR words after them, each in a column of its own so every read is naturally aligned and no
+  // row is padded except 5 machines' (3 words in one vector): 16 / 20 B a row, 1,280 / 1,600 B
+  // for 5 / 10 machines. The larger job buckets keep the loop over the set's rows, and so do
+  // 20 machines: their 3,200 B end the fifth resident workgroup of pfsp_front_kernel<20, 20>
+  // (5 x 35,200 B against a CU's 163,840 B), which three engines on one GPU use: ta021 9.20 ->
+  // 9.66 s with the table, one engine 13.6 -> 13.0 s (profiles/r12/full_and_regress.txt).
+  static constexpr bool RTAB = NJ <= 20 && M <= 10;
+  static constexpr int TROWS = kRemainGroups * kRemainPats;
+  static constexpr int TQ = (HW + 1) / 4;
+  static constexpr int TR = HW > 4 * TQ ? HW - 4 * TQ : 0;
+  static_assert(TR <= 2, "the words after a row's vectors are read as one u32 or one uint2");
+  static constexpr int TVEC = TROWS * (4 * TQ + TR) / 4;  // the table in 16-B vectors
   // wave-balanced emit (front_emit_balanced): survivor descriptors a wave lists at a time.
   // Up to 10 machines; 20 machines keep the per-lane loop: the fetched parent copy (22
   // words) takes pfsp_front_kernel<20, 20> from 93 to 105 VGPRs, 5 to 4 waves per SIMD
@@ -121,9 +134,12 @@ struct FrontGeom {
 template <int M, int NJ = 20>
 struct PfspFrontArgs {
   PoolArgs<PfspFrontNode<M, NJ>> pool;
-  const uint16_t* ptab;  // job-major p, [jobs][MS], padded machines 0
+  // job-major p, [jobs][MS], padded machines 0; where FrontGeom::RTAB, the remain table follows
+  // at u16 NJ * MS (FrontRemTab's bytes: pfsp_front_fill_args)
+  const uint16_t* ptab;
   int jobs;
   int min_tails[M];      // padded machines: 0
+  uint32_t tails2[(M + 1) / 2];  // the same as packed u16 pairs (machine 2h low, 2h + 1 high)
   // bounds kernel only (tests): bounds of parent i's children at bounds_out[offsets[i] + rank of
   // the job among the parent's unscheduled jobs]
   const PfspFrontNode<M, NJ>* parents_in;
@@ -176,8 +192,23 @@ __device__ inline void front_stamp(const A& a, int k) {
   }
 }
 
+// The remain table in LDS (20-job bucket up to 10 machines; empty in the others): row g * kRemainPats + pat is
+// the packed sum of the p rows of the jobs of pattern pat of bit group g. Same bytes as the
+// image the host appends to the p table.
+template <int M, int NJ, bool ON = FrontGeom<M, NJ>::RTAB>
+struct FrontRemTab {};
+template <int M, int NJ>
+struct FrontRemTab<M, NJ, true> {
+  using G = FrontGeom<M, NJ>;
+  uint4 tq[G::TQ][G::TROWS];
+  uint32_t tr[G::TR > 0 ? G::TROWS : 1][G::TR > 0 ? G::TR : 1];
+};
+static_assert(sizeof(FrontRemTab<5, 20>) == 16 * FrontGeom<5, 20>::TVEC + 16 &&
+                  sizeof(FrontRemTab<10, 20>) == 16 * FrontGeom<10, 20>::TVEC,
+              "the table's LDS bytes are the host image's (5 machines: one unused vector after it)");
+
 template <int M, int NJ = 20>
-struct FrontSmem {
+struct FrontSmem : FrontRemTab<M, NJ> {
   using G = FrontGeom<M, NJ>;
   uint16_t ptab[G::NJ][G::MS];
   int scan[kBlock / kWave];
@@ -211,6 +242,13 @@ struct FrontSmem {
   // (front_emit_balanced; a wave touches its own row only)
   uint16_t desc[kBlock / kWave][G::BAL ? G::DW : 1];
 };
+// (20 jobs, up to 10 machines with the remain table: 23,424 / 26,432 B for 5 / 10 machines,
+// 32,000 B for 20. Up to 10 machines the six workgroups of the register budget fit, one more
+// than the grid holds, which several engines on one GPU use; 20 machines fit five)
+static_assert(FrontGeom<5, 20>::WAVES * sizeof(FrontSmem<5, 20>) <= 160 * 1024 &&
+                  FrontGeom<10, 20>::WAVES * sizeof(FrontSmem<10, 20>) <= 160 * 1024 &&
+                  (FrontGeom<20, 20>::GRID_WGS + 1) * sizeof(FrontSmem<20, 20>) <= 160 * 1024,
+              "the 20-job grids' resident workgroups fit a CU's LDS");
 static_assert(FrontGeom<5, 100>::GRID_WGS * sizeof(FrontSmem<5, 100>) <= 160 * 1024 &&
                   FrontGeom<10, 100>::GRID_WGS * sizeof(FrontSmem<10, 100>) <= 160 * 1024 &&
                   FrontGeom<20, 100>::GRID_WGS * sizeof(FrontSmem<20, 100>) <= 160 * 1024,
@@ -350,28 +388,46 @@ __device__ inline void front_dbg(const PfspFrontArgs<M, NJ>& a, int kind, const 
 // value, remain + tail and bound covers at most jobs + machines - 1 cells of the matrix
 // (the staircase rule, core/pfsp_front.hpp), and (jobs + machines - 1) * max p < 65536.
 
-// Bounds of the children appending the jobs of `rest` to a parent whose front / remain +
-// tail are fb[m] / rb[m] (each value in both halves): emit(j, lb) per job, ascending,
-// two jobs per pass (ref add_front_and_bound, c_bound_simple.c:219-244).
+// Half m & 1 of a packed word in both halves. (Next to its packed op the compiler folds the
+// selection into the op's op_sel; in front_bounds_x2 the selections do not depend on the
+// pair pass and are hoisted ahead of the loop, one v_perm_b32 and one VGPR each.)
+__device__ inline u16x2 front_half(uint32_t x, int m) {
+  const u16x2 v = as_u16x2(x);
+  return (m & 1) ? __builtin_shufflevector(v, v, 1, 1) : __builtin_shufflevector(v, v, 0, 0);
+}
+
+// Bounds of the children appending the jobs of `rest` to the parent held in w (its fronts:
+// the node's packed words) whose remain + tail per machine are the packed words rt:
+// emit(j, lb) per job, ascending, two jobs per pass (ref add_front_and_bound,
+// c_bound_simple.c:219-244). The pair chain reads the parent's half of a word for both
+// children (front_half) straight from the packed words: no unpack, add and duplicate per
+// machine (two or three instructions each for the fronts and for remain + tail before).
 template <int M, int NJ, class Emit>
-__device__ inline void front_bounds_x2(const FrontSmem<M, NJ>& sm, const uint32_t (&fb)[M], const uint32_t (&rb)[M],
+__device__ inline void front_bounds_x2(const FrontSmem<M, NJ>& sm, const uint32_t (&w)[FrontGeom<M, NJ>::NW],
+                                       const uint32_t (&rt)[FrontGeom<M, NJ>::HW],
                                        typename FrontGeom<M, NJ>::Mask rest, Emit emit) {
-  constexpr int HW = FrontGeom<M, NJ>::HW;
+  constexpr int HW = FrontGeom<M, NJ>::HW, FO = FrontGeom<M, NJ>::FO;
   // 20 machines: one child per pass (same-box A/B on ta021 LB1_d: packed pairs 9.82 s,
   // one child 9.31 s; on ta014's 10 machines the pairs win, 0.2245 -> 0.2209 ms:
-  // profiles/r4/packed_bounds_ab.txt)
+  // profiles/r4/packed_bounds_ab.txt), on plain 32-bit values unpacked once per parent
   if constexpr (M > 10) {
+    int f[M], r[M];
+#pragma unroll
+    for (int m = 0; m < M; ++m) {
+      f[m] = front_of<M, NJ>(w, m);
+      r[m] = static_cast<int>((rt[m >> 1] >> ((m & 1) * 16)) & 0xffffu);
+    }
     mask_words(rest, [&](auto x, int base) {
       for (; x; x &= x - 1) {
         const int j = base + mask_ctz(x);
         int pr[M];
         front_row<M, NJ>(sm.ptab[j], pr);
-        int lb = static_cast<int>(fb[0] & 0xffffu) + static_cast<int>(rb[0] & 0xffffu);
-        int tt = static_cast<int>(fb[0] & 0xffffu) + pr[0];
+        int lb = f[0] + r[0];
+        int tt = f[0] + pr[0];
 #pragma unroll
         for (int m = 1; m < M; ++m) {
-          const int sv = max(tt, static_cast<int>(fb[m] & 0xffffu));
-          lb = max(lb, sv + static_cast<int>(rb[m] & 0xffffu));
+          const int sv = max(tt, f[m]);
+          lb = max(lb, sv + r[m]);
           tt = sv + pr[m];
         }
         emit(j, lb);
@@ -394,13 +450,13 @@ __device__ inline void front_bounds_x2(const FrontSmem<M, NJ>& sm, const uint32_
         a[h] = r1[h];
         b[h] = r2[h];
       }
-      u16x2 lb = as_u16x2(fb[0]) + as_u16x2(rb[0]);
-      u16x2 tt = as_u16x2(fb[0]) + as_u16x2(__builtin_amdgcn_perm(b[0], a[0], 0x05040100u));
+      u16x2 lb = front_half(w[FO], 0) + front_half(rt[0], 0);
+      u16x2 tt = front_half(w[FO], 0) + as_u16x2(__builtin_amdgcn_perm(b[0], a[0], 0x05040100u));
 #pragma unroll
       for (int m = 1; m < M; ++m) {
         const u16x2 pm = as_u16x2(__builtin_amdgcn_perm(b[m >> 1], a[m >> 1], (m & 1) ? 0x07060302u : 0x05040100u));
-        const u16x2 sv = __builtin_elementwise_max(tt, as_u16x2(fb[m]));
-        lb = __builtin_elementwise_max(lb, sv + as_u16x2(rb[m]));
+        const u16x2 sv = __builtin_elementwise_max(tt, front_half(w[FO + (m >> 1)], m));
+        lb = __builtin_elementwise_max(lb, sv + front_half(rt[m >> 1], m));
         tt = sv + pm;
       }
       const uint32_t l = as_u32(lb);
@@ -410,25 +466,57 @@ __device__ inline void front_bounds_x2(const FrontSmem<M, NJ>& sm, const uint32_
   });
 }
 
-// fb / rb of a parent: its front (words of w) and its packed remain rp plus the tails
+// remain + tail of a parent as packed words: its packed remain rp plus the packed tails
+// (no carry between the halves: remain + tail fits 16 bits, pfsp_front_ok)
 template <int M, int NJ>
-__device__ inline void front_broadcast(const PfspFrontArgs<M, NJ>& a, const uint32_t (&w)[FrontGeom<M, NJ>::NW],
-                                       const uint32_t (&rp)[FrontGeom<M, NJ>::HW], uint32_t (&fb)[M], uint32_t (&rb)[M]) {
+__device__ inline void front_remain_tail(const PfspFrontArgs<M, NJ>& a, const uint32_t (&rp)[FrontGeom<M, NJ>::HW],
+                                         uint32_t (&rt)[FrontGeom<M, NJ>::HW]) {
 #pragma unroll
-  for (int m = 0; m < M; ++m) {
-    fb[m] = static_cast<uint32_t>(front_of<M, NJ>(w, m)) * 0x10001u;
-    rb[m] = (((rp[m >> 1] >> ((m & 1) * 16)) & 0xffffu) + static_cast<uint32_t>(a.min_tails[m])) * 0x10001u;
-  }
+  for (int h = 0; h < FrontGeom<M, NJ>::HW; ++h) rt[h] = rp[h] + a.tails2[h];
 }
 
 // The packed remain of the node in w: the sum of its unscheduled jobs' p rows.
 template <int M, int NJ>
 __device__ inline void front_remain(const FrontSmem<M, NJ>& sm, const uint32_t (&w)[FrontGeom<M, NJ>::NW],
                                     uint32_t (&r2)[FrontGeom<M, NJ>::HW]) {
-  constexpr int HW = FrontGeom<M, NJ>::HW;
+  using G = FrontGeom<M, NJ>;
+  constexpr int HW = G::HW;
 #pragma unroll
   for (int h = 0; h < HW; ++h) r2[h] = 0;
-  if constexpr (M <= 10) {
+  if constexpr (G::RTAB) {
+    // 20 jobs, up to 10 machines: one table row per group of kRemainBits set bits
+    // (FrontRemTab), whatever the depth: kRemainGroups independent row reads, then the adds.
+    // (The loop over the set's rows costs a pass of 4 row reads and an LDS wait per 4
+    // unscheduled jobs.) An empty set (a lane without a node) reads the zero rows.
+    const uint32_t x = w[G::MO];
+    int row[kRemainGroups];
+#pragma unroll
+    for (int g = 0; g < kRemainGroups; ++g)
+      row[g] = g * kRemainPats + static_cast<int>((x >> (kRemainBits * g)) & (kRemainPats - 1));
+    uint32_t rw[kRemainGroups][4 * G::TQ + 2];
+#pragma unroll
+    for (int g = 0; g < kRemainGroups; ++g) {
+#pragma unroll
+      for (int q = 0; q < G::TQ; ++q) {
+        const uint4 v = sm.tq[q][row[g]];
+        rw[g][4 * q] = v.x;
+        rw[g][4 * q + 1] = v.y;
+        rw[g][4 * q + 2] = v.z;
+        rw[g][4 * q + 3] = v.w;
+      }
+      if constexpr (G::TR == 1) {
+        rw[g][4 * G::TQ] = sm.tr[row[g]][0];
+      } else if constexpr (G::TR == 2) {
+        const uint2 v = *reinterpret_cast<const uint2*>(sm.tr[row[g]]);
+        rw[g][4 * G::TQ] = v.x;
+        rw[g][4 * G::TQ + 1] = v.y;
+      }
+    }
+#pragma unroll
+    for (int g = 0; g < kRemainGroups; ++g)
+#pragma unroll
+      for (int h = 0; h < HW; ++h) r2[h] += rw[g][h];
+  } else if constexpr (M <= 10) {
     // 4 jobs per pass, every row read issued before the first add: one LDS latency per
     // pass instead of one per job (the rolled loop waited on each row in turn; ta014
     // headline -0.9 % same box, profiles/r6/remain_ab.txt). 20 machines keep the rolled
@@ -474,9 +562,9 @@ template <int M, int NJ, class A, class Emit>
 __device__ inline void front_parent_r(const A& a, const FrontSmem<M, NJ>& sm,
                                       const uint32_t (&w)[FrontGeom<M, NJ>::NW], const uint32_t (&rp)[FrontGeom<M, NJ>::HW],
                                       Emit emit, int kind) {
-  uint32_t fb[M], rb[M];
-  front_broadcast<M, NJ>(a, w, rp, fb, rb);
-  front_bounds_x2<M, NJ>(sm, fb, rb, front_mask<M, NJ>(w), [&](int j, int lb) {
+  uint32_t rt[FrontGeom<M, NJ>::HW];
+  front_remain_tail<M, NJ>(a, rp, rt);
+  front_bounds_x2<M, NJ>(sm, w, rt, front_mask<M, NJ>(w), [&](int j, int lb) {
     if (front_rec(a)) front_dbg<M, NJ>(a, kind, w, rp, j, lb);
     emit(j, lb);
   });
@@ -485,13 +573,9 @@ __device__ inline void front_parent_r(const A& a, const FrontSmem<M, NJ>& sm,
 template <int M, int NJ, class A, class Emit>
 __device__ inline void front_parent(const A& a, const FrontSmem<M, NJ>& sm,
                                     const uint32_t (&w)[FrontGeom<M, NJ>::NW], Emit emit, int kind = kDbgOne) {
-  uint32_t rp[FrontGeom<M, NJ>::HW], fb[M], rb[M];
+  uint32_t rp[FrontGeom<M, NJ>::HW];
   front_remain<M, NJ>(sm, w, rp);
-  front_broadcast<M, NJ>(a, w, rp, fb, rb);
-  front_bounds_x2<M, NJ>(sm, fb, rb, front_mask<M, NJ>(w), [&](int j, int lb) {
-    if (front_rec(a)) front_dbg<M, NJ>(a, kind, w, rp, j, lb);
-    emit(j, lb);
-  });
+  front_parent_r<M, NJ>(a, sm, w, rp, emit, kind);
 }
 
 // Child of the parent in w that appends job j: depth + 1, j removed from the set, and
@@ -792,23 +876,26 @@ __device__ inline int front_expand_tp_regs(const A& a, FrontSmem<M, NJ>& sm,
   using G = FrontGeom<M, NJ>;
   constexpr int HW = G::HW;
   typename G::Mask surv{};
-  int nsurv = 0;
   const bool leaf = static_cast<int>(w[0] & FrontGeom<M, NJ>::DMASK) + 1 == a.jobs;
+  int nkept = 0, lbmin = INT_MAX;
   {
-    uint32_t fb[M], rb[M];
-    front_broadcast<M, NJ>(a, w, rp, fb, rb);
-    front_bounds_x2<M, NJ>(sm, fb, rb, front_mask<M, NJ>(w), [&](int j, int lb) {
+    uint32_t rt[HW];
+    front_remain_tail<M, NJ>(a, rp, rt);
+    front_bounds_x2<M, NJ>(sm, w, rt, front_mask<M, NJ>(w), [&](int j, int lb) {
       if (front_rec(a)) front_dbg<M, NJ>(a, kind, w, rp, j, lb);
       const bool kp = keep(static_cast<int>(threadIdx.x), j);
-      if (leaf) {
-        nleaf += kp;
-        if (lb < best) atomicMin(&a.pool.ctl->best.v, lb);
-      } else if (kp && lb < best) {
-        ++nsurv;
-        mask_set(surv, j);
-      }
+      nkept += kp;
+      lbmin = min(lbmin, lb);
+      if (kp && lb < best) mask_set(surv, j);
     });
   }
+  // (leaf parents after the loop, as in front_local)
+  if (leaf) {
+    nleaf += nkept;
+    if (lbmin < best) atomicMin(&a.pool.ctl->best.v, lbmin);
+    surv = typename G::Mask{};
+  }
+  const int nsurv = mask_count(surv);
   int tot = 0;
   int idx = block_exclusive_scan(nsurv, sm.scan, &tot);
   // (the per-lane loop stays here: the balanced emit in this path too put the 10-machine
@@ -1051,21 +1138,27 @@ __device__ inline void front_local(const A& a, FrontSmem<M, NJ>& sm, const IterV
         top -= npop;
       }
       typename G::Mask surv{};
-      int nsurv = 0;
+      int nsurv = 0, lbmin = INT_MAX;  // (the lowest child bound: a leaf parent's makespans)
       const bool leaf = static_cast<int>(w[0] & FrontGeom<M, NJ>::DMASK) + 1 == a.jobs;
       if (!have_r) front_remain<M, NJ>(sm, w, rp);
       front_parent_r<M, NJ>(
           a, sm, w, rp,
           [&](int j, int lb) {
-            if (leaf) {
-              ++nleaf;
-              if (lb < best) atomicMin(&pa.ctl->best.v, lb);
-            } else if (lb < best) {
-              ++nsurv;
-              mask_set(surv, j);
-            }
+            lbmin = min(lbmin, lb);
+            if (lb < best) mask_set(surv, j);
           },
           kDbgLocal);
+      // leaf parents (depth jobs - 1, one child each) are handled here, once per step, not in
+      // every pass of the pair loop (the pass is one straight block without the leaf branch
+      // and the incumbent update in it: 68 vector and 17 scalar instructions instead of 79
+      // and 50, ta014 -2.2 %, profiles/r12/headline_ab.txt): their children are leaves,
+      // counted and compared with the incumbent, never pushed
+      if (leaf) {
+        nleaf += mask_count(front_mask<M, NJ>(w));
+        if (lbmin < best) atomicMin(&pa.ctl->best.v, lbmin);
+        surv = typename G::Mask{};
+      }
+      nsurv = mask_count(surv);
       int tot = 0;
       const int off = block_exclusive_scan(nsurv, sm.scan, &tot);
       // will another step run? then the children it pops (the last min(top, kBlock)
@@ -1557,6 +1650,17 @@ void pfsp_front_kernel(FrontArgsT<M, NJ, INSTR> a, int t) {
     const int x = tid + i * kBlock;
     ptv[i] = x < a.jobs * G::MS ? a.ptab[x] : 0;
   }
+  // (and the remain table's, where the bucket has one: one 16-B load per thread)
+  constexpr int TVN = G::RTAB ? (G::TVEC + kBlock - 1) / kBlock : 0;
+  uint4 tv[TVN > 0 ? TVN : 1];
+  if constexpr (G::RTAB) {
+    const uint4* const tsrc = reinterpret_cast<const uint4*>(a.ptab + G::NJ * G::MS);
+#pragma unroll
+    for (int i = 0; i < TVN; ++i) {
+      const int x = tid + i * kBlock;
+      tv[i] = x < G::TVEC ? tsrc[x] : make_uint4(0, 0, 0, 0);
+    }
+  }
   const IterView v =
       pool_begin<Node, G::MAXCHUNKS>(pa, t, G::BP, sm.pool, a.bpf, G::LT, G::NJ * (G::NJ - 1), G::LMAX, INSTR && G::DYN);
   front_stamp(a, 1);
@@ -1566,6 +1670,12 @@ void pfsp_front_kernel(FrontArgsT<M, NJ, INSTR> a, int t) {
 #pragma unroll
     for (int i = 0; i < PTN; ++i)
       if (tid + i * kBlock < G::NJ * G::MS) pt[tid + i * kBlock] = ptv[i];
+    if constexpr (G::RTAB) {
+      uint4* const td = reinterpret_cast<uint4*>(static_cast<FrontRemTab<M, NJ>*>(&sm));
+#pragma unroll
+      for (int i = 0; i < TVN; ++i)
+        if (tid + i * kBlock < G::TVEC) td[tid + i * kBlock] = tv[i];
+    }
   }
   const int best = prune_best(pa, v);
   Node* const bout = pa.buf[(t & 1) ^ 1];
@@ -1612,19 +1722,26 @@ void pfsp_front_kernel(FrontArgsT<M, NJ, INSTR> a, int t) {
     }
     Mask surv{};
     int nsurv = 0, nleaf = 0;
+    int lbmin = INT_MAX;
     front_parent<M, NJ>(
         a, sm, w,
         [&](int j, int lb) {
-          const bool keep = mask_test(kmask, j);
-          if (leaf) {
-            nleaf += keep;
-            if (lb < best) atomicMin(&pa.ctl->best.v, lb);
-          } else if (keep && lb < best) {
+          lbmin = min(lbmin, lb);
+          if (mask_test(kmask, j) && lb < best) {
             ++nsurv;
             mask_set(surv, j);
           }
         },
         v.split ? kDbgSplit : kDbgOne);
+    if (leaf) {
+      // (after the loop, as in front_local: the kept children of a leaf parent are counted,
+      // every child's bound is compared with the incumbent, none survives)
+      const Mask rest = front_mask<M, NJ>(w);
+      nleaf = mask_count(rest) - mask_count(mask_andnot(rest, kmask));
+      if (lbmin < best) atomicMin(&pa.ctl->best.v, lbmin);
+      surv = Mask{};
+      nsurv = 0;
+    }
     if (first) front_stamp(a, 4);
     // one scan for both counts: survivors (<= 256 x (NJ - 1)) in bits 0 to SB - 1 (13 bits
     // for 20 jobs, 15 above), leaves (<= 256) in the 9 bits above them
@@ -1659,6 +1776,11 @@ __global__ __launch_bounds__(kBlock) void pfsp_front_bounds_kernel(PfspFrontArgs
   __shared__ FrontSmem<M, NJ> sm;
   uint16_t* pt = &sm.ptab[0][0];
   for (int i = threadIdx.x; i < a.jobs * G::MS; i += kBlock) pt[i] = a.ptab[i];
+  if constexpr (G::RTAB) {
+    const uint4* const tsrc = reinterpret_cast<const uint4*>(a.ptab + G::NJ * G::MS);
+    uint4* const td = reinterpret_cast<uint4*>(static_cast<FrontRemTab<M, NJ>*>(&sm));
+    for (int i = threadIdx.x; i < G::TVEC; i += kBlock) td[i] = tsrc[i];
+  }
   __syncthreads();
   for (int i = blockIdx.x * kBlock + threadIdx.x; i < a.nparents; i += gridDim.x * kBlock) {
     uint32_t w[G::NW];

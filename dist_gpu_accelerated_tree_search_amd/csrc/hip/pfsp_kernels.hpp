@@ -759,6 +759,14 @@ __device__ inline void pfsp_expand_lb2(const PfspArgs<NJ, M>& a, int t) {
   const int ndouble = (N + 7) >> 3;
   unsigned long long tm[4] = {0, 0, 0, 0}, tc = 0;
   const bool timed = a.dbg_time != nullptr;
+  // Element-wise probe (a.dbg_lb, tests): a walk is not skipped because another wave has
+  // already raised the child's maximum to the incumbent, so the bound recorded for a pruned
+  // child is the maximum over all pairs of its rounds and does not depend on which wave got
+  // there first. (Skipping is a race by design: any value >= best prunes. Which children
+  // survive is the same either way.) The skip tests compare with `skip`, the incumbent or,
+  // under the probe, a value no bound reaches: no instruction more in the walks' loops
+  // (a flag tested next to the comparison cost ta056 1.5 %).
+  const int skip = a.dbg_lb != nullptr ? INT_MAX : best;
   const bool stride = a.lb2_stride != 0;
   int nchunks_done = 0;
   const unsigned long long t_pro = a.dbg_blk ? wall_clock64() : 0;
@@ -866,7 +874,7 @@ __device__ inline void pfsp_expand_lb2(const PfspArgs<NJ, M>& a, int t) {
           while (qq < nq) {
             const int ca = sm.alist[2 * kk];
             const int cb = 2 * kk + 1 < na ? sm.alist[2 * kk + 1] : -1;
-            const bool la = sm.lbv[ca] < best, lbb = cb >= 0 && sm.lbv[cb] < best;
+            const bool la = sm.lbv[ca] < skip, lbb = cb >= 0 && sm.lbv[cb] < skip;
             if (la || lbb) {
               const uint2 pi = sm.pinfo[q0 + qq];
               const int m0 = pi.x & 0xff, m1 = (pi.x >> 8) & 0xff;
@@ -908,7 +916,7 @@ __device__ inline void pfsp_expand_lb2(const PfspArgs<NJ, M>& a, int t) {
           const int uref = __ballot(qq != qf) == 0
                                ? __builtin_amdgcn_readfirstlane(static_cast<int>(sm.pinfo[q0 + qf].x >> 16))
                                : -1;
-          if (sm.lbv[ai] < best) {
+          if (sm.lbv[ai] < skip) {
             const uint2 pi = sm.pinfo[q0 + qq];
             int t0 = sm.cf[pi.x & 0xff][ai], t1 = sm.cf[(pi.x >> 8) & 0xff][ai];
             u64 msk[G::NW];
@@ -958,7 +966,7 @@ __device__ inline void pfsp_expand_lb2(const PfspArgs<NJ, M>& a, int t) {
         const int qf = __builtin_amdgcn_readfirstlane(q);
         const int uref =
             __ballot(q != qf) == 0 ? __builtin_amdgcn_readfirstlane(static_cast<int>(sm.pinfo[qf].x >> 16)) : -1;
-        if (sm.lbv[ai] < best) {
+        if (sm.lbv[ai] < skip) {
           const uint2 pi = sm.pinfo[q];
           int t0 = sm.cf[pi.x & 0xff][ai], t1 = sm.cf[(pi.x >> 8) & 0xff][ai];
           u64 msk[G::NW];
