@@ -9,6 +9,7 @@
 #include "../core/drivers_cpu.hpp"
 #include "../core/estimate.hpp"
 #include "../core/pfsp_front.hpp"
+#include "../core/pool_ring.hpp"
 #include "../core/pool_window.hpp"
 #include "../core/shm_control.hpp"
 #include "engine_binding.hpp"
@@ -165,6 +166,45 @@ PYBIND11_MODULE(_tts_cpu, m) {
       "A pool iteration's window of B parents dealt over `spread` chunks of at most `cap` parents (pool_begin): "
       "(parents per chunk of an even spread, parents per chunk, chunks). wide: the 64-bit form the kernels' 32-bit "
       "arithmetic replaced (core/pool_window.hpp).");
+  // the device ring's host bookkeeping (core/pool_ring.hpp; the engine's ring refers to its
+  // control block's words, this one to two words of its own)
+  struct OwnedRing {
+    PoolRing::Word bot, stack;
+    PoolRing r;
+    OwnedRing(size_t cap, size_t b, size_t s) : bot(b), stack(s), r(cap, &bot, &stack) {
+      if (cap == 0 || (cap & (cap - 1)) || b >= cap) throw std::invalid_argument("PoolRing: cap = 2^k > bot");
+    }
+    OwnedRing(const OwnedRing&) = delete;
+  };
+  py::class_<OwnedRing>(m, "PoolRing")
+      .def(py::init<size_t, size_t, size_t>(), py::arg("cap"), py::arg("bot") = 0, py::arg("stack") = 0)
+      .def_readonly("bot", &OwnedRing::bot)
+      .def_readonly("stack", &OwnedRing::stack)
+      .def("top", [](const OwnedRing& o) { return o.r.top(); })
+      .def("spans",
+           [](const OwnedRing& o, size_t start, size_t n) {
+             std::vector<std::pair<size_t, size_t>> out;
+             for (const RingSpan& s : o.r.spans(start, n)) out.emplace_back(s.offset, s.count);
+             return out;
+           })
+      .def("under_bottom", [](const OwnedRing& o, size_t k) { return o.r.under_bottom(k); })
+      .def("contiguous_under_bottom", [](const OwnedRing& o) { return o.r.contiguous_under_bottom(); })
+      .def("pop_bottom", [](OwnedRing& o, size_t n) { o.r.pop_bottom(n); })
+      .def("push_top", [](OwnedRing& o, size_t n) { o.r.push_top(n); })
+      .def("extend_bottom", [](OwnedRing& o, size_t k) { o.r.extend_bottom(k); })
+      .def("reset", [](OwnedRing& o, size_t n) { o.r.reset(n); });
+  py::class_<ReplayPlan>(m, "ReplayPlan")
+      .def(py::init<int, int, int, size_t, size_t, size_t>(), py::arg("iters_small"), py::arg("iters_large"),
+           py::arg("iters_first"), py::arg("buf_nodes"), py::arg("cap"), py::arg("max_parents"))
+      .def_property_readonly("ks", &ReplayPlan::ks)
+      .def("growth", &ReplayPlan::growth)
+      .def("pick", &ReplayPlan::pick, py::arg("total"), py::arg("extra"), py::arg("reserved"), py::arg("fresh"),
+           py::arg("kmax") = SIZE_MAX)
+      .def("fits", &ReplayPlan::fits)
+      .def("leave_kmax", &ReplayPlan::leave_kmax)
+      .def("exportable_ahead", &ReplayPlan::exportable_ahead<std::vector<int>>)
+      .def("refill_limit", &ReplayPlan::refill_limit)
+      .def("spill_ahead_keep", &ReplayPlan::spill_ahead_keep);
   m.def("pfsp_fronts_fit_u16", &pfsp_fronts_fit_u16,
         "Every prefix completion time fits 16 bits (the GPU LB2 kernels' condition; sufficient, not necessary).");
   m.def(

@@ -32,6 +32,7 @@
 #include <vector>
 
 #include "../core/engine_api.hpp"
+#include "../core/pool_ring.hpp"
 #include "device_resource.hpp"
 #include "host_spill.hpp"
 #include "pool_device.hpp"
@@ -46,10 +47,12 @@ struct traits_dyn<T, std::void_t<decltype(T::kDyn)>> : std::bool_constant<T::kDy
 
 // Traits contract:
 //   using Node; using Args (with a `PoolArgs<Node> pool` member);
-//   static constexpr int kParentsPerChunk, kChildrenPerChunk, kMaxChunks;
+//   static constexpr int kParentsPerChunk, kChildrenPerChunk, kMaxChunks, kMaxChildren (per parent),
+//                        kLocalSteps, kLocalMin (local DFS: steps at most, default window threshold);
+//   static constexpr bool kDyn (optional: dynamic local DFS iterations, traits_dyn above);
 //   static void launch(const Args&, int t, int grid, hipStream_t);
-//   static void flatten(const dev::PoolArgs<Node>&, int grid, hipStream_t);
-//   static void finalize(const dev::PoolArgs<Node>&, hipStream_t);
+//   static void flatten(const dev::PoolArgs<Node>&, int buf, int grid, hipStream_t);
+//   static void finalize(const dev::PoolArgs<Node>&, int buf, int slot, hipStream_t);
 //   static int blocks_per_cu();
 template <class Traits>
 class DeviceEngine final : public IEngine, public DeviceResource {
@@ -111,6 +114,7 @@ class DeviceEngine final : public IEngine, public DeviceResource {
     TTS_HIP_CHECK(hipStreamCreateWithFlags(&xfer_, hipStreamNonBlocking));
 #endif
     std::memset(h_ctl_, 0, sizeof(dev::PoolCtl));
+    ring_ = PoolRing(cap_, &h_ctl_->bot, &h_ctl_->slot[0].stack);
     h_ctl_->best.v = 0x7fffffff;
     h_ctl_->dive_shift = cfg_.dive_shift;
     if (cfg_.external_stream) {
@@ -209,17 +213,12 @@ class DeviceEngine final : public IEngine, public DeviceResource {
     }
     // graphs of 6, 12, 24, ... iterations up to iters_large; run() picks one from
     // the pool size and the worst-case ring growth
-    // (and the first replay's length, when it is not one of them)
+    // (and the first replay's length, when it is not one of them: core/pool_ring.hpp)
     if (const char* f = std::getenv("TTS_ITERS_FIRST")) cfg_.iters_first = std::max(6, std::atoi(f) / 6 * 6);
-    for (int k = cfg_.iters_small; k <= cfg_.iters_large; k *= 2) ks_.push_back(k);
-    if (cfg_.iters_first % 6 == 0 && cfg_.iters_first < cfg_.iters_large &&
-        std::find(ks_.begin(), ks_.end(), cfg_.iters_first) == ks_.end()) {
-      ks_.push_back(cfg_.iters_first);
-      std::sort(ks_.begin(), ks_.end());
-    }
+    plan_ = ReplayPlan(cfg_.iters_small, cfg_.iters_large, cfg_.iters_first, buf_nodes_, cap_, cfg_.max_parents);
     if (cfg_.use_graphs)
       for (int ph = 0; ph < 2; ++ph)
-        for (int k : ks_)
+        for (int k : plan_.ks())
           for (int m = 0; m < 2; ++m) graphs_[ph][m].push_back(capture(k, m, 3 * ph));
     if (const char* f = std::getenv("TTS_LEARN_FIRST")) learn_first_ = std::atoi(f) != 0;
     TTS_HIP_CHECK(hipStreamSynchronize(stream_));
@@ -430,13 +429,11 @@ class DeviceEngine final : public IEngine, public DeviceResource {
     }
   }
   bool in_flight() override { return !inflight_.empty(); }
-  // With a replay in flight: what can be exported from under it (export_ahead) — the
-  // ring part the running replays cannot reach — so a plan built on this size never
-  // asks for more than the pool can give without waiting; at least 1 (the replay is work).
   // With a replay in flight: the pool as of the last completed replay (plus the host
   // spill), the size the round's needy / donor / termination decisions use (at least 1:
   // the replay is work), and separately what can be exported from under the running
-  // replays without waiting (export_ahead), the cap on what the plan asks of this rank.
+  // replays without waiting (export_ahead: the ring part they cannot reach), the cap on
+  // what the plan asks of this rank.
   size_t size_known() override {
     if (inflight_.empty()) return size();
     const size_t held = dev_total() + spill_.size() + refill_n_;
@@ -568,10 +565,8 @@ class DeviceEngine final : public IEngine, public DeviceResource {
       }
       int gi = pick_graph(total, 0);
       // right after begin(): as many iterations as the previous solve took, when known
-      const int kf = (fresh_ && learn_first_ && learned_k_ > 0 &&
-                      total + reserved_ + static_cast<size_t>(learned_k_ + 1) * buf_nodes_ <= cap_)
-                         ? learned_k_
-                         : 0;
+      const bool learned = fresh_ && learn_first_ && learned_k_ > 0 && plan_.fits(total, reserved_, learned_k_);
+      const int kf = learned ? learned_k_ : 0;
       if (gi < 0) {
         if (!resv_.empty()) {  // ring span still being copied out: wait for the oldest copy
           TTS_HIP_CHECK(hipEventSynchronize(resv_.front().first));
@@ -594,7 +589,7 @@ class DeviceEngine final : public IEngine, public DeviceResource {
       // growth of both fits; then read the older graph's mirror. Hides the host
       // sync + launch gap between replays. ----
       size_t known = total;
-      size_t inflight_growth = static_cast<size_t>((kf ? kf : ks_[gi]) + 1) * buf_nodes_;
+      size_t inflight_growth = plan_.growth(kf ? kf : plan_.ks()[gi]);
       bool hook_stop = false, leaving = false;
       while (!inflight_.empty()) {
         const bool budget_ok = !hook_stop && (max_launches < 0 || launches < max_launches) &&
@@ -603,8 +598,7 @@ class DeviceEngine final : public IEngine, public DeviceResource {
         // (only a replay short enough that half of the pool stays exportable from under
         // it, as leave_one's: a long one would hide a donor's pool from the plan)
         if (overlap_ && !budget_ok && inflight_.size() == 1 && (max_launches < 0 || launches < max_launches) &&
-            leave_ok(known) &&
-            static_cast<size_t>(inflight_k_.front()) <= std::max<size_t>(6, known / 2 / cfg_.max_parents)) {
+            leave_ok(known) && static_cast<size_t>(inflight_k_.front()) <= plan_.leave_kmax(known)) {
           leaving = true;
           ++stats_.left_inflight;
           break;
@@ -614,13 +608,13 @@ class DeviceEngine final : public IEngine, public DeviceResource {
           if (g2 >= 0) {
             launch_graph(g2);
             ++launches;
-            inflight_growth += static_cast<size_t>(ks_[g2] + 1) * buf_nodes_;
+            inflight_growth += plan_.growth(plan_.ks()[g2]);
           }
         }
         wait_oldest();
         check_overflow();
         known = dev_total();
-        inflight_growth = inflight_.empty() ? 0 : static_cast<size_t>(inflight_k_.front() + 1) * buf_nodes_;
+        inflight_growth = inflight_.empty() ? 0 : plan_.growth(inflight_k_.front());
         // a long pipelined stretch still answers the hook (live pool size for siblings
         // and peers, stop requests); a better incumbent from it is applied once nothing
         // is in flight, at the top of the outer loop
@@ -669,15 +663,14 @@ class DeviceEngine final : public IEngine, public DeviceResource {
     h_ctl_->tree = h_ctl_->sol = h_ctl_->parents = h_ctl_->iters = 0;
     for (auto& x : h_ctl_->xacc) x.tree = x.sol = 0;
     h_ctl_->best.v = best;
-    h_ctl_->bot = 0;
-    h_ctl_->slot[0].stack = 0;
+    ring_.reset(0);
     h_ctl_->slot[0].nch = 0;
     h_ctl_->pend_children = h_ctl_->pend_leaves = h_ctl_->pend_internal = 0;
     h_ctl_->overflow = 0;
     if (n <= kStageNodes) {
       // one load kernel reads the control block and the nodes from mapped pinned memory
       if (loader_pending_) TTS_HIP_CHECK(hipStreamSynchronize(stream_));  // it still reads the staging area
-      h_ctl_->slot[0].stack = n;
+      ring_.reset(n);
       std::memcpy(h_begin_, h_ctl_, sizeof(dev::PoolCtl));
       Node* stage = reinterpret_cast<Node*>(reinterpret_cast<char*>(h_begin_) + kUpBytes);
       std::memcpy(stage, nodes, n * sizeof(Node));
@@ -719,7 +712,7 @@ class DeviceEngine final : public IEngine, public DeviceResource {
     for (int p = 0; p < passes; ++p) {
       if (h_ctl_->overflow) throw std::runtime_error("device pool overflow (ring too small)");
       const size_t total = dev_total();
-      if (total == 0 || total + 7 * buf_nodes_ > cap_) break;
+      if (total == 0 || !plan_.fits(total, 0, 6)) break;
       auto a = args_;
       a.pool.max_parents = static_cast<int>(win);
       a.pool.prune_fixed = 1;
@@ -758,8 +751,7 @@ class DeviceEngine final : public IEngine, public DeviceResource {
           TTS_HIP_CHECK(hipFree(tmp));
         }
       }
-      h_ctl_->bot = 0;
-      h_ctl_->slot[0].stack = keep;
+      ring_.reset(keep);
       if (!spill_.empty()) spill_.keep_strided(rank, world);
       if (rank != 0) h_ctl_->tree = h_ctl_->sol = h_ctl_->parents = h_ctl_->iters = 0;
       upload_ctl();
@@ -844,8 +836,7 @@ class DeviceEngine final : public IEngine, public DeviceResource {
     // a replay short enough that half of the pool stays exportable from under it
     // (exportable_ahead): a donor still looks like one to the round's plan (a 4-rank
     // skewed start lost its balance behind 48-iteration replays)
-    const size_t kmax = std::max<size_t>(6, total / 2 / cfg_.max_parents);
-    const int gi = pick_graph(total, 0, kmax);
+    const int gi = pick_graph(total, 0, plan_.leave_kmax(total));
     if (gi < 0) return false;
     launch_graph(gi);
     start_spill_ahead();
@@ -859,19 +850,14 @@ class DeviceEngine final : public IEngine, public DeviceResource {
   // the replays have completed (commit_export).
   size_t exportable_ahead() const {
     if (ahead_n_ || refill_n_ || !resv_.empty()) return 0;
-    size_t k = 0;
-    for (int x : inflight_k_) k += static_cast<size_t>(x);
-    const size_t safe = (k + 1) * cfg_.max_parents;
-    const size_t stack = dev_stack() - export_pending_;
-    return stack > safe ? stack - safe : 0;
+    return plan_.exportable_ahead(dev_stack(), export_pending_, inflight_k_);
   }
   bool export_ahead(Node* dst, size_t n) {
     if (exportable_ahead() < n) return false;
-    const size_t start = (h_ctl_->bot + export_pending_) & (cap_ - 1);
-    const size_t first = std::min(n, cap_ - start);
-    TTS_HIP_CHECK(hipMemcpyAsync(dst, d_ring_ + start, first * sizeof(Node), hipMemcpyDeviceToDevice, xs()));
-    if (first < n)
-      TTS_HIP_CHECK(hipMemcpyAsync(dst + first, d_ring_, (n - first) * sizeof(Node), hipMemcpyDeviceToDevice, xs()));
+    for (const RingSpan& s : ring_.spans(ring_.bot() + export_pending_, n)) {
+      TTS_HIP_CHECK(hipMemcpyAsync(dst, d_ring_ + s.offset, s.count * sizeof(Node), hipMemcpyDeviceToDevice, xs()));
+      dst += s.count;
+    }
     export_pending_ += n;
     // the ring span is handed back to the compute stream only after this copy
     // (commit_export makes the stream wait for it: a replay that wraps around the ring
@@ -888,8 +874,7 @@ class DeviceEngine final : public IEngine, public DeviceResource {
       TTS_HIP_CHECK(hipStreamWaitEvent(stream_, ev_ahead_, 0));
       ahead_copy_ = false;
     }
-    h_ctl_->bot = (h_ctl_->bot + export_pending_) & (cap_ - 1);
-    h_ctl_->slot[0].stack -= export_pending_;
+    ring_.pop_bottom(export_pending_);
     export_pending_ = 0;
     upload_ctl();
   }
@@ -906,7 +891,7 @@ class DeviceEngine final : public IEngine, public DeviceResource {
       throw std::runtime_error("pool outgrew the parent window before the armed rank split (set_split)");
     if (h_ctl_->overflow) throw std::runtime_error("device pool overflow (ring too small)");
   }
-  size_t dev_stack() const { return static_cast<size_t>(h_ctl_->slot[0].stack); }
+  size_t dev_stack() const { return ring_.stack(); }
   size_t dev_buf() const { return static_cast<size_t>(h_ctl_->pend_children); }
   size_t dev_total() const { return dev_stack() + dev_buf(); }
 
@@ -957,21 +942,9 @@ class DeviceEngine final : public IEngine, public DeviceResource {
     ++stats_.syncs;
     stats_.t_memcpy += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
   }
-  // Largest graph whose worst-case ring growth (plus `extra` already in flight)
-  // fits, no longer than the pool size suggests: 6 iterations while ramping up or
-  // draining, more when the pool holds several parent windows.
+  // The graph for a pool of `total` nodes with `extra` growth already in flight (ReplayPlan::pick).
   int pick_graph(size_t total, size_t extra, size_t kmax = SIZE_MAX) const {
-    // right after begin(): one long replay (iters_first) — a graph boundary costs
-    // ~50 us of host sync + relaunch, an empty iteration ~4.5 us (profiles/r1/r1f)
-    size_t want = fresh_ ? std::max<size_t>(6, static_cast<size_t>(cfg_.iters_first)) : 6;
-    while (want < static_cast<size_t>(cfg_.iters_large) && total >= (want / 6) * 2 * cfg_.max_parents &&
-           want * 2 <= kmax)
-      want *= 2;
-    for (int i = static_cast<int>(ks_.size()) - 1; i >= 0; --i) {
-      if (static_cast<size_t>(ks_[i]) > want && i > 0) continue;
-      if (total + extra + reserved_ + static_cast<size_t>(ks_[i] + 1) * buf_nodes_ <= cap_) return i;
-    }
-    return -1;
+    return plan_.pick(total, extra, reserved_, fresh_, kmax);
   }
   // Asynchronous upload of the host shadow (through its own pinned staging copy,
   // so the shadow can be edited again immediately).
@@ -1002,11 +975,10 @@ class DeviceEngine final : public IEngine, public DeviceResource {
       h_ctl_->pend_leaves = h_ctl_->pend_internal = 0;
       return;
     }
-    if (dev_stack() + c > cap_) throw std::runtime_error("device ring capacity exceeded");
-    // the flatten kernel reads the device ctl, which equals the host shadow here
+    ring_.push_top(c);  // (throws when the ring cannot hold them, before the launch)
+    // the flatten kernel reads the device ctl, which the host shadow equalled until here
     Traits::flatten(args_.pool, phase_ & 1, grid_, stream_);
     TTS_HIP_CHECK(hipGetLastError());
-    h_ctl_->slot[0].stack += c;
     h_ctl_->tree += c + h_ctl_->pend_internal;
     h_ctl_->sol += h_ctl_->pend_leaves;
     h_ctl_->slot[0].nch = 0;
@@ -1015,24 +987,22 @@ class DeviceEngine final : public IEngine, public DeviceResource {
   }
 
   void ring_write_top(const Node* src, size_t n, hipMemcpyKind kind) {
-    if (n == 0) return;
-    if (dev_stack() + n > cap_) throw std::runtime_error("device ring capacity exceeded");
-    const size_t start = (h_ctl_->bot + dev_stack()) & (cap_ - 1);
-    const size_t first = std::min(n, cap_ - start);
-    TTS_HIP_CHECK(hipMemcpyAsync(d_ring_ + start, src, first * sizeof(Node), kind, stream_));
-    if (first < n) TTS_HIP_CHECK(hipMemcpyAsync(d_ring_, src + first, (n - first) * sizeof(Node), kind, stream_));
-    h_ctl_->slot[0].stack += n;
+    const size_t top = ring_.top();
+    ring_.push_top(n);  // (throws before any copy)
+    for (const RingSpan& s : ring_.spans(top, n)) {
+      TTS_HIP_CHECK(hipMemcpyAsync(d_ring_ + s.offset, src, s.count * sizeof(Node), kind, stream_));
+      src += s.count;
+    }
   }
 
   void ring_read_bottom(Node* dst, size_t n, hipMemcpyKind kind) {
     if (n == 0) return;
-    const size_t start = h_ctl_->bot & (cap_ - 1);
-    const size_t first = std::min(n, cap_ - start);
-    TTS_HIP_CHECK(hipMemcpyAsync(dst, d_ring_ + start, first * sizeof(Node), kind, stream_));
-    if (first < n) TTS_HIP_CHECK(hipMemcpyAsync(dst + first, d_ring_, (n - first) * sizeof(Node), kind, stream_));
+    for (const RingSpan& s : ring_.spans(ring_.bot(), n)) {
+      TTS_HIP_CHECK(hipMemcpyAsync(dst, d_ring_ + s.offset, s.count * sizeof(Node), kind, stream_));
+      dst += s.count;
+    }
     if (kind != hipMemcpyDeviceToDevice) TTS_HIP_CHECK(hipStreamSynchronize(stream_));
-    h_ctl_->bot = (h_ctl_->bot + n) & (cap_ - 1);
-    h_ctl_->slot[0].stack -= n;
+    ring_.pop_bottom(n);
   }
 
   // Pinned spill blocks: 1/16 of the ring, between 64K nodes and 256 MB.
@@ -1082,18 +1052,15 @@ class DeviceEngine final : public IEngine, public DeviceResource {
     n = std::min(n, dev_stack());
     if (n == 0) return;
     order(stream_, xs());  // the nodes were written by earlier replays
-    const size_t start = h_ctl_->bot & (cap_ - 1);
-    const size_t first = std::min(n, cap_ - start);
     auto reserve = [&](hipEvent_t ev, size_t k) {
       resv_.emplace_back(ev, k);
       reserved_ += k;
     };
     const hipEvent_t tr = trace_ ? trace_mark(xs()) : nullptr;
-    spill_.push_from_device(d_ring_ + start, first, xs(), reserve);
-    if (first < n) spill_.push_from_device(d_ring_, n - first, xs(), reserve);
+    for (const RingSpan& s : ring_.spans(ring_.bot(), n))
+      spill_.push_from_device(d_ring_ + s.offset, s.count, xs(), reserve);
     if (tr) trace_rec_.push_back({1, tr, trace_mark(xs())});
-    h_ctl_->bot = (h_ctl_->bot + n) & (cap_ - 1);
-    h_ctl_->slot[0].stack -= n;
+    ring_.pop_bottom(n);
     stats_.spilled += n;
   }
   // Spill ahead, overlapped with the replays. Past 3/4 of the ring, right after a graph
@@ -1106,22 +1073,19 @@ class DeviceEngine final : public IEngine, public DeviceResource {
   // completed (commit_spill_ahead, nothing in flight).
   void start_spill_ahead() {
     if (ahead_n_ || !resv_.empty() || dev_stack() <= cap_ / 4 * 3) return;
-    const size_t keep = std::max(cap_ / 2, 2 * static_cast<size_t>(ks_.back() + 1) * cfg_.max_parents);
+    const size_t keep = plan_.spill_ahead_keep();
     if (dev_stack() <= keep) return;
     const size_t n = dev_stack() - keep;
-    const size_t start = h_ctl_->bot & (cap_ - 1);
-    const size_t first = std::min(n, cap_ - start);
     auto reserve = [&](hipEvent_t ev, size_t k) { ahead_.emplace_back(ev, k); };
     const hipEvent_t tr = trace_ ? trace_mark(xs()) : nullptr;
-    spill_.push_from_device(d_ring_ + start, first, xs(), reserve);
-    if (first < n) spill_.push_from_device(d_ring_, n - first, xs(), reserve);
+    for (const RingSpan& s : ring_.spans(ring_.bot(), n))
+      spill_.push_from_device(d_ring_ + s.offset, s.count, xs(), reserve);
     if (tr) trace_rec_.push_back({1, tr, trace_mark(xs())});
     ahead_n_ = n;
   }
   void commit_spill_ahead() {
     if (!ahead_n_) return;
-    h_ctl_->bot = (h_ctl_->bot + ahead_n_) & (cap_ - 1);
-    h_ctl_->slot[0].stack -= ahead_n_;
+    ring_.pop_bottom(ahead_n_);
     for (auto& r : ahead_) {
       resv_.push_back(r);
       reserved_ += r.second;
@@ -1138,17 +1102,12 @@ class DeviceEngine final : public IEngine, public DeviceResource {
   bool start_refill(size_t want) {
     if (refill_n_ || spill_.empty() || want == 0) return false;
     flush_load();
-    // like push_host: the device part stays within half the ring, and the smallest
-    // graph must still fit afterwards (else refills and spills would alternate)
-    const size_t used = dev_total() + reserved_;
-    const size_t growth = static_cast<size_t>(ks_.front() + 1) * buf_nodes_;
-    const size_t limit = std::min(cap_ / 2, cap_ > growth ? cap_ - growth : 0);
-    if (used >= limit) return false;
-    const size_t b0 = h_ctl_->bot & (cap_ - 1);
+    const size_t room = plan_.refill_limit(dev_total() + reserved_);
+    if (room == 0) return false;
     // one pinned block at most, contiguous under the ring bottom
-    const size_t k = std::min({want, spill_.top_count(), limit - used, b0 ? b0 : cap_});
+    const size_t k = std::min({want, spill_.top_count(), room, ring_.contiguous_under_bottom()});
     if (k == 0) return false;
-    Node* dst = d_ring_ + ((b0 + cap_ - k) & (cap_ - 1));
+    Node* dst = d_ring_ + ring_.under_bottom(k);
     const hipEvent_t tr = trace_ ? trace_mark(xs()) : nullptr;
     if (spill_.pop_to_device(dst, k, xs(), &refill_ev_) != k) throw std::logic_error("pinned spill: short refill");
     if (tr) trace_rec_.push_back({2, tr, trace_mark(xs())});
@@ -1163,8 +1122,7 @@ class DeviceEngine final : public IEngine, public DeviceResource {
   }
   void fold_refill() {
     TTS_HIP_CHECK(hipStreamWaitEvent(stream_, refill_ev_, 0));
-    h_ctl_->bot = (h_ctl_->bot + cap_ - refill_n_) & (cap_ - 1);
-    h_ctl_->slot[0].stack += refill_n_;
+    ring_.extend_bottom(refill_n_);
     reserved_ -= refill_n_;
     stats_.refilled += refill_n_;
     refill_n_ = 0;
@@ -1179,7 +1137,7 @@ class DeviceEngine final : public IEngine, public DeviceResource {
   void launch_graph(int gi, int K = 0) {
     const int m = next_mirror_;
     next_mirror_ ^= 1;
-    const int k = K > 0 ? K : ks_[gi];
+    const int k = K > 0 ? K : plan_.ks()[gi];
     const bool with_load = load_deferred_ && K > 0 && cfg_.use_graphs;
     if (!with_load) flush_load();
     const hipEvent_t tr = trace_ ? trace_mark(stream_) : nullptr;
@@ -1333,8 +1291,9 @@ class DeviceEngine final : public IEngine, public DeviceResource {
   int arm_world_ = 0, arm_rank_ = 0;  // split armed for the next begin() (set_split)
   size_t arm_min_ = 1;
   hipStream_t stream_ = nullptr, own_stream_ = nullptr;
-  std::vector<int> ks_;
-  std::vector<hipGraphExec_t> graphs_[2][2];  // [start phase 0 / 3][mirror][graph]
+  PoolRing ring_;     // ring geometry over h_ctl_'s bot / slot[0].stack words (core/pool_ring.hpp)
+  ReplayPlan plan_;   // the graphs' iteration counts and which one fits
+  std::vector<hipGraphExec_t> graphs_[2][2];  // [start phase 0 / 3][mirror][graph of plan_.ks()]
   std::map<int, std::array<hipGraphExec_t, 2>> first_graphs_;  // learned first replays by length
   int phase_ = 0;         // t of the next iteration: 0 or 3
   bool learn_first_ = true;  // first replay after begin() = the previous solve's iterations (TTS_LEARN_FIRST=0: off)

@@ -85,3 +85,37 @@ def test_pop_push_roundtrip_preserves_nodes():
     out = eng.pop(len(nodes))
     assert len(out) == len(nodes)
     assert sorted(map(bytes, np.asarray(out))) == sorted(map(bytes, np.asarray(nodes)))
+
+
+def test_pop_and_push_across_the_ring_wrap_keep_the_tree():
+    # the host path over the ring's wrap. The frontier fills half the ring from slot 0, the rest
+    # waits in the pinned spill. Half a ring is more than the smallest graph leaves room for
+    # (2^19 slots, 7 x 40,960 of growth), so the first run() spills the bottom half: the bottom
+    # moves up by `spilled` slots, and every refill moves it down again. Once more has come
+    # back than went out, the bottom lies refilled - spilled slots under slot 0, at the ring's
+    # end, and a stack that holds more than that runs over slot 0. Refills start below 32 K
+    # device nodes and a replay pops at most 6 x 1024, so far more than the refilled block's
+    # nodes are still there when the loop sees it.
+    model = PfspModel(14, 1)
+    eng = model.make_engine("gpu", 0, EngineOptions(max_parents=1024, ring_bytes=1 << 20))
+    nodes, t1, s1, best = model.warmup(model.initial_best(1), 400_000)
+    eng.begin(nodes, int(best))
+    st = eng.stats()
+    assert len(nodes) > st["capacity"] // 2 and st["host_nodes"] > 0 and st["device_nodes"] == st["capacity"] // 2
+    for _ in range(1000):
+        eng.run(max_launches=1)
+        st = eng.stats()
+        if st["refilled"] > st["spilled"]:
+            break
+    under = st["refilled"] - st["spilled"]
+    assert 0 < under < st["device_nodes"] <= st["capacity"] // 2, st
+    n = eng.size()
+    assert n == st["device_nodes"] + st["host_nodes"]
+    out = eng.pop(n)  # ring_read_bottom across the wrap
+    assert len(out) == n and eng.size() == 0
+    eng.push(out)  # ring_write_top
+    assert eng.size() == n
+    eng.run()
+    st = eng.stats()
+    assert (t1 + st["tree"], s1 + st["sol"], st["best"]) == GOLD14
+    assert st["host_nodes"] == 0 and st["device_nodes"] == 0
