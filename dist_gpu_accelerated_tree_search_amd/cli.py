@@ -17,6 +17,9 @@ pfsp:  -D 0            CPU only: -C threads (0/1 = sequential, ref pfsp_c / pfsp
                            the distributed driver).
                        -w / -L enable work sharing inside a node / across nodes.
        --streams K     K engines per GPU, run concurrently (large trees).
+       --estimate P    no search: Knuth tree-size estimate of the -u 1 tree from P random
+                       probes, on device 0 (-D >= 1) or on the host twin (-D 0, -C threads);
+                       --estimate-seed S. Honours --json.
 nqueens: -D 0 CPU sequential (ref nqueens_c), -D >= 1 GPU(s).
 Results: the reference's stdout blocks, plus a CSV row (singlegpu.csv,
 multigpu.csv or dist_multigpu.csv) and optionally a JSON record (--json).
@@ -72,10 +75,29 @@ def _pfsp_parser(cls=argparse.ArgumentParser) -> argparse.ArgumentParser:
                     help="LB1 / LB1_d on 51-500 jobs: front-carrying nodes (256- and 512-bit job sets above 100 "
                          "jobs) instead of permutation nodes; includes --front-wide (sets TTS_FRONT_WIDE=2 for "
                          "this process and every rank it spawns)")
+    ap.add_argument("--estimate", type=int, default=None, metavar="PROBES",
+                    help="no search: Knuth estimate of the -u 1 tree from this many random probes, on device 0 "
+                         "(-D >= 1) or on the host twin with -C threads (-D 0)")
+    ap.add_argument("--estimate-seed", type=int, default=1, help="seed of the --estimate probes")
     ap.add_argument("--json", default=None, help="append a JSON run record to this file")
     ap.add_argument("--csv-dir", default=".", help="directory of the CSV statistics files")
     ap.add_argument("--no-csv", action="store_true")
     return ap
+
+
+def _pfsp_estimate(a, model) -> int:
+    from .search import estimate_tree
+
+    if a.estimate < 1:
+        sys.stderr.write("Error: --estimate needs a positive number of probes\n")
+        return 1
+    e = estimate_tree(model, probes=a.estimate, seed=a.estimate_seed, device=None if a.D == 0 else 0,
+                      threads=max(1, a.C))
+    print(report.pfsp_estimate(a.inst, a.lb, e))
+    if a.json:
+        report.write_json_record(a.json, {**model.describe(), "estimate": True, "seed": a.estimate_seed,
+                                          "n_gpus": 0 if a.D == 0 else 1, **e})
+    return 0
 
 
 def _validate_pfsp(a) -> None:
@@ -187,6 +209,8 @@ def pfsp_main(argv: list[str]) -> int:
 
     world_env = int(os.environ.get("WORLD_SIZE", "1"))
     model = PfspModel(a.inst, a.lb)
+    if a.estimate is not None:
+        return _pfsp_estimate(a, model)
     if a.D == 0:
         version = 0 if a.C <= 1 else 2
         print(report.pfsp_settings(a.inst, model.machines, model.jobs, a.ub, a.lb, 0, a.C, a.ws, 1, a.L, version))

@@ -13,6 +13,7 @@
 #include "../core/pool_window.hpp"
 #include "../core/shm_control.hpp"
 #include "engine_binding.hpp"
+#include "estimate_binding.hpp"
 
 namespace py = pybind11;
 using namespace tts;
@@ -453,6 +454,38 @@ PYBIND11_MODULE(_tts_cpu, m) {
       },
       py::arg("model"), py::arg("best"), py::arg("probes") = 1000, py::arg("seed") = 1, py::arg("threads") = 1,
       "Knuth random-probe estimate of the explored tree for a fixed incumbent (core/estimate.hpp).");
+  m.def(
+      "tree_estimate_indexed",
+      [](py::object model, int best, unsigned long long probes, unsigned long long seed,
+         unsigned long long first_probe, int threads, bool records) {
+        // a PfspModel (its native instance), or any object with jobs, machines, lb and a
+        // machine-major p: the only way to a 1-job instance
+        const int lb = model.attr("lb").cast<int>();
+        PfspInstance own;
+        const PfspInstance* in = nullptr;
+        if (py::hasattr(model, "native") && py::isinstance<PfspInstance>(model.attr("native"))) {
+          in = &model.attr("native").cast<const PfspInstance&>();
+        } else {
+          own = make_estimate_instance(model.attr("jobs").cast<int>(), model.attr("machines").cast<int>(),
+                                       model.attr("p").cast<std::vector<int>>());
+          in = &own;
+        }
+        TreeEstimate e;
+        ProbeRecords rec;
+        {
+          py::gil_scoped_release nogil;
+          e = with_pfsp_bucket(in->jobs, [&](auto nj) {
+            return knuth_estimate_indexed(PfspProblem<decltype(nj)::value>(*in, lb), best, first_probe, probes, seed,
+                                          threads, records ? &rec : nullptr);
+          });
+        }
+        return estimate_dict(e, records ? &rec : nullptr);
+      },
+      py::arg("model"), py::arg("best"), py::arg("probes"), py::arg("seed"), py::arg("first_probe") = 0,
+      py::arg("threads") = 1, py::arg("records") = false,
+      "Host twin of the device estimator: probes first_probe .. first_probe + probes - 1 of the indexed Knuth "
+      "estimate (survivors by ascending job, choices from core/probe_rng.hpp), the same whatever `threads`. "
+      "records: per-probe est, depth and chosen jobs (-1 past the depth), at most 2^20 probes.");
   m.def(
       "pfsp_drain",
       [](const PfspInstance& in, int lb, int best, U8 nodes) {

@@ -11,11 +11,13 @@
 #include "../core/cpu_engine.hpp"
 #include "../core/pfsp_front.hpp"
 #include "../core/problems.hpp"
+#include "../hip/estimate_device.hpp"
 #include "../hip/host_support.hpp"
 #include "../hip/pfsp_engine.hpp"
 #include "../hip/queens_engine.hpp"
 #include "../hip/rccl_transport.hpp"
 #include "engine_binding.hpp"
+#include "estimate_binding.hpp"
 
 namespace py = pybind11;
 using namespace tts;
@@ -221,6 +223,39 @@ PYBIND11_MODULE(_tts_hip, m) {
       py::arg("N"), py::arg("G") = 1, py::arg("device") = 0, py::arg("max_parents") = size_t(1) << 20,
       py::arg("ring_bytes") = size_t(16) << 30, py::arg("iters_small") = 6, py::arg("iters_large") = 48,
       py::arg("use_graphs") = true, py::arg("stream") = 0, py::arg("iters_first") = 24);
+
+  m.def(
+      "tree_estimate",
+      [](int jobs, int machines, std::vector<int> p, int lb, int best, unsigned long long probes,
+         unsigned long long seed, unsigned long long first_probe, int device, bool records, unsigned long long batch,
+         int max_blocks) {
+        const PfspInstance in = make_estimate_instance(jobs, machines, std::move(p));
+        DeviceEstimate r;
+        {
+          py::gil_scoped_release nogil;
+          r = pfsp_device_estimate(in, lb, best, first_probe, probes, seed, device, records, batch, max_blocks);
+        }
+        py::dict d = estimate_dict(r.est, records ? &r.records : nullptr);
+        py::dict l;
+        l["batch"] = r.batch;
+        l["rate"] = r.rate;
+        l["grid"] = r.grid;
+        l["waves"] = r.waves;
+        l["first_seconds"] = r.first_seconds;
+        l["lds_bytes"] = r.lds_bytes;
+        l["launches"] = r.launches;
+        l["seconds"] = r.seconds;
+        d["launch"] = l;
+        return d;
+      },
+      py::arg("jobs"), py::arg("machines"), py::arg("p"), py::arg("lb"), py::arg("best"), py::arg("probes"),
+      py::arg("seed"), py::arg("first_probe") = 0, py::arg("device") = 0, py::arg("records") = false,
+      py::arg("batch") = 0, py::arg("max_blocks") = 0,
+      "Device Knuth estimate of the explored PFSP tree for a fixed incumbent: probes first_probe .. first_probe + "
+      "probes - 1 of _tts_cpu.tree_estimate_indexed, one wave per probe (hip/estimate_kernels.hpp). The host "
+      "binding's dict plus `launch`: probes per launch (batch 0: sized from the first launch's rate), that rate, "
+      "the grid, the launches and their seconds. max_blocks > 0 caps the workgroups of a launch. ValueError for an "
+      "instance outside the accepted ranges.");
 
   m.def(
       "pfsp_bounds",

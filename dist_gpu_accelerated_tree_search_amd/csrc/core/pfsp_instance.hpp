@@ -125,6 +125,23 @@ inline PfspInstance make_instance(int jobs, int machines, std::vector<int> p_mac
   return in;
 }
 
+// Instance of a tree-size estimate (core/estimate.hpp) from plain data. As make_instance, and a
+// single job is allowed too (its root has one leaf child and nothing is pushed: the estimate is 0).
+inline PfspInstance make_estimate_instance(int jobs, int machines, std::vector<int> p, int best_known = INT_MAX) {
+  if (jobs >= 2) return make_instance(jobs, machines, std::move(p), 0, best_known);
+  if (jobs != 1 || machines < 2) throw std::invalid_argument("PFSP estimate needs >= 1 job and >= 2 machines");
+  if (static_cast<int>(p.size()) != machines) throw std::invalid_argument("processing-time matrix has the wrong size");
+  PfspInstance in;
+  in.jobs = 1;
+  in.machines = machines;
+  in.best_known = best_known;
+  in.p = p;
+  in.pj = std::move(p);
+  detail::fill_heads_tails(in);
+  detail::fill_lb2_tables(in);
+  return in;
+}
+
 inline PfspInstance make_taillard_instance(int id) {
   return make_instance(taillard_jobs(id), taillard_machines(id), taillard_processing_times(id), id,
                        taillard_best_ub(id));

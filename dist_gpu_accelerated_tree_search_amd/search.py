@@ -50,6 +50,41 @@ def progress_weights(model) -> list[float]:
     return w
 
 
+def estimate_tree(model, best: int | None = None, probes: int = 1 << 16, seed: int = 1, device: int | None = 0,
+                  first_probe: int = 0, threads: int = 1, records: bool = False, batch: int = 0) -> dict:
+    """Knuth estimate of the tree a PFSP search explores from a fixed incumbent `best`
+    (None: model.best_known, the -u 1 tree), from `probes` random root-to-dead-end walks.
+
+    device >= 0: the device estimator (csrc/hip/estimate_kernels.hpp, one wave per probe,
+    bounded launches); device None: its host twin on `threads` threads
+    (csrc/core/estimate.hpp knuth_estimate_indexed). Probe i of (seed, first_probe) is
+    the same walk on both, so the two agree probe for probe and differ only in the order
+    their sums are added. Returns tree, stderr, depth, probes, per_level (mean estimated
+    nodes per level), best, device, seconds, probes_per_s and launch (the device's launch
+    record: probes per launch and the rate that sized them; None on the host), plus
+    records (per-probe est, depth, jobs) when asked. N-Queens stays on
+    ops.cpu().tree_estimate."""
+    if getattr(model, "kind", "pfsp") != "pfsp":
+        raise ValueError("estimate_tree is for PFSP models; N-Queens uses ops.cpu().tree_estimate")
+    best = int(model.best_known if best is None else best)
+    t0 = time.perf_counter()
+    if device is None:
+        r = dict(ops.cpu().tree_estimate_indexed(model, best, int(probes), int(seed), first_probe=int(first_probe),
+                                                 threads=int(threads), records=bool(records)))
+        r["launch"] = None
+    else:
+        H = ops.require_gpu(device)
+        p = model.native.p if hasattr(model, "native") else model.p
+        r = dict(H.tree_estimate(int(model.jobs), int(model.machines), [int(x) for x in p], int(model.lb), best,
+                                 int(probes), int(seed), first_probe=int(first_probe), device=int(device),
+                                 records=bool(records), batch=int(batch)))
+    r["seconds"] = time.perf_counter() - t0
+    r["probes_per_s"] = r["probes"] / r["seconds"] if r["seconds"] > 0 else float("inf")
+    r["best"] = best
+    r["device"] = device
+    return r
+
+
 def solve_cpu(model, ub: int = 1, threads: int = 0, m: int = 25, batch: int = 20000, steal_cap: int = 250000,
               ws: bool = True, verbose: bool = False) -> SolveResult:
     """threads == 0: sequential (ref pfsp_c.c / nqueens_c.c); >0: multi-core WS
