@@ -19,7 +19,10 @@ pfsp:  -D 0            CPU only: -C threads (0/1 = sequential, ref pfsp_c / pfsp
        --streams K     K engines per GPU, run concurrently (large trees).
        --estimate P    no search: Knuth tree-size estimate of the -u 1 tree from P random
                        probes, on device 0 (-D >= 1) or on the host twin (-D 0, -C threads);
-                       --estimate-seed S. Honours --json.
+                       --estimate-seed S. Honours --json. --estimate-method lookahead:
+                       importance-weighted probes (child c followed in proportion to its
+                       surviving children to the power --estimate-power 1..3, counted under
+                       --estimate-look own|lb1; default own for -l 0/1, lb1 for -l 2).
 nqueens: -D 0 CPU sequential (ref nqueens_c), -D >= 1 GPU(s).
 Results: the reference's stdout blocks, plus a CSV row (singlegpu.csv,
 multigpu.csv or dist_multigpu.csv) and optionally a JSON record (--json).
@@ -79,6 +82,14 @@ def _pfsp_parser(cls=argparse.ArgumentParser) -> argparse.ArgumentParser:
                     help="no search: Knuth estimate of the -u 1 tree from this many random probes, on device 0 "
                          "(-D >= 1) or on the host twin with -C threads (-D 0)")
     ap.add_argument("--estimate-seed", type=int, default=1, help="seed of the --estimate probes")
+    ap.add_argument("--estimate-method", choices=["knuth", "lookahead"], default="knuth",
+                    help="--estimate probes: uniform child choice (knuth) or one-level lookahead, child c in "
+                         "proportion to (c's surviving children) ** --estimate-power")
+    ap.add_argument("--estimate-power", type=int, choices=[1, 2, 3], default=2,
+                    help="power of the lookahead weights")
+    ap.add_argument("--estimate-look", choices=["own", "lb1"], default=None,
+                    help="bound that counts a child's surviving children for the lookahead weights: the model's own "
+                         "or LB1 (default: own for -l 0/1, lb1 for -l 2)")
     ap.add_argument("--json", default=None, help="append a JSON run record to this file")
     ap.add_argument("--csv-dir", default=".", help="directory of the CSV statistics files")
     ap.add_argument("--no-csv", action="store_true")
@@ -92,7 +103,7 @@ def _pfsp_estimate(a, model) -> int:
         sys.stderr.write("Error: --estimate needs a positive number of probes\n")
         return 1
     e = estimate_tree(model, probes=a.estimate, seed=a.estimate_seed, device=None if a.D == 0 else 0,
-                      threads=max(1, a.C))
+                      threads=max(1, a.C), method=a.estimate_method, power=a.estimate_power, look=a.estimate_look)
     print(report.pfsp_estimate(a.inst, a.lb, e))
     if a.json:
         report.write_json_record(a.json, {**model.describe(), "estimate": True, "seed": a.estimate_seed,

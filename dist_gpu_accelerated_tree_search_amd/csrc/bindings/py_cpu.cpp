@@ -457,10 +457,12 @@ PYBIND11_MODULE(_tts_cpu, m) {
   m.def(
       "tree_estimate_indexed",
       [](py::object model, int best, unsigned long long probes, unsigned long long seed,
-         unsigned long long first_probe, int threads, bool records) {
+         unsigned long long first_probe, int threads, bool records, const std::string& method, int power,
+         py::object look) {
         // a PfspModel (its native instance), or any object with jobs, machines, lb and a
         // machine-major p: the only way to a 1-job instance
         const int lb = model.attr("lb").cast<int>();
+        const EstimateMethod how = parse_estimate_method(method, power, look, lb);
         PfspInstance own;
         const PfspInstance* in = nullptr;
         if (py::hasattr(model, "native") && py::isinstance<PfspInstance>(model.attr("native"))) {
@@ -475,17 +477,24 @@ PYBIND11_MODULE(_tts_cpu, m) {
         {
           py::gil_scoped_release nogil;
           e = with_pfsp_bucket(in->jobs, [&](auto nj) {
-            return knuth_estimate_indexed(PfspProblem<decltype(nj)::value>(*in, lb), best, first_probe, probes, seed,
-                                          threads, records ? &rec : nullptr);
+            const PfspProblem<decltype(nj)::value> prob(*in, lb);
+            if (how.lookahead)
+              return lookahead_estimate_indexed(prob, best, first_probe, probes, seed, how.power, how.look, threads,
+                                                records ? &rec : nullptr);
+            return knuth_estimate_indexed(prob, best, first_probe, probes, seed, threads, records ? &rec : nullptr);
           });
         }
         return estimate_dict(e, records ? &rec : nullptr);
       },
       py::arg("model"), py::arg("best"), py::arg("probes"), py::arg("seed"), py::arg("first_probe") = 0,
-      py::arg("threads") = 1, py::arg("records") = false,
+      py::arg("threads") = 1, py::arg("records") = false, py::arg("method") = "knuth", py::arg("power") = 2,
+      py::arg("look") = py::none(),
       "Host twin of the device estimator: probes first_probe .. first_probe + probes - 1 of the indexed Knuth "
       "estimate (survivors by ascending job, choices from core/probe_rng.hpp), the same whatever `threads`. "
-      "records: per-probe est, depth and chosen jobs (-1 past the depth), at most 2^20 probes.");
+      "records: per-probe est, depth and chosen jobs (-1 past the depth), at most 2^20 probes. "
+      "method 'lookahead': importance-weighted probes (core/estimate.hpp lookahead_estimate_indexed), child c "
+      "followed in proportion to (its surviving children)^power, power 1..3, counted under look = 'own' (the "
+      "model's bound) or 'lb1' (None: own for lb 0/1, lb1 for lb 2).");
   m.def(
       "pfsp_drain",
       [](const PfspInstance& in, int lb, int best, U8 nodes) {

@@ -228,12 +228,13 @@ PYBIND11_MODULE(_tts_hip, m) {
       "tree_estimate",
       [](int jobs, int machines, std::vector<int> p, int lb, int best, unsigned long long probes,
          unsigned long long seed, unsigned long long first_probe, int device, bool records, unsigned long long batch,
-         int max_blocks) {
+         int max_blocks, const std::string& method, int power, py::object look) {
+        const EstimateMethod how = parse_estimate_method(method, power, look, lb);
         const PfspInstance in = make_estimate_instance(jobs, machines, std::move(p));
         DeviceEstimate r;
         {
           py::gil_scoped_release nogil;
-          r = pfsp_device_estimate(in, lb, best, first_probe, probes, seed, device, records, batch, max_blocks);
+          r = pfsp_device_estimate(in, lb, best, first_probe, probes, seed, device, records, batch, max_blocks, how);
         }
         py::dict d = estimate_dict(r.est, records ? &r.records : nullptr);
         py::dict l;
@@ -250,12 +251,14 @@ PYBIND11_MODULE(_tts_hip, m) {
       },
       py::arg("jobs"), py::arg("machines"), py::arg("p"), py::arg("lb"), py::arg("best"), py::arg("probes"),
       py::arg("seed"), py::arg("first_probe") = 0, py::arg("device") = 0, py::arg("records") = false,
-      py::arg("batch") = 0, py::arg("max_blocks") = 0,
+      py::arg("batch") = 0, py::arg("max_blocks") = 0, py::arg("method") = "knuth", py::arg("power") = 2,
+      py::arg("look") = py::none(),
       "Device Knuth estimate of the explored PFSP tree for a fixed incumbent: probes first_probe .. first_probe + "
       "probes - 1 of _tts_cpu.tree_estimate_indexed, one wave per probe (hip/estimate_kernels.hpp). The host "
       "binding's dict plus `launch`: probes per launch (batch 0: sized from the first launch's rate), that rate, "
-      "the grid, the launches and their seconds. max_blocks > 0 caps the workgroups of a launch. ValueError for an "
-      "instance outside the accepted ranges.");
+      "the grid, the launches and their seconds. max_blocks > 0 caps the workgroups of a launch. method 'lookahead', "
+      "power and look: the importance-weighted probes of the host binding (lookahead_probe_kernel). ValueError for "
+      "an instance outside the accepted ranges or an unknown method, power or look.");
 
   m.def(
       "pfsp_bounds",

@@ -12,12 +12,20 @@
 //   h(seed, probe)  = mix(seed + G * (probe + 1))           once per probe
 //   r(h, level)     = mix(h + G * (level + 1))              level = depth of the parent, 0 at the root
 //   pick(r, k)      = ((r >> 32) * k) >> 32                 index among k survivors, 0 <= pick < k
+//   pick_weighted(r, T) = (r * T) >> 64                     the high half of the 64 x 64 product, 0 <= x < T
 //
 // The survivors are ordered by the job they append, ascending; pick is an index into
-// that order. k is at most the number of jobs (< 2^32).
+// that order. k is at most the number of jobs (< 2^32). A lookahead probe
+// (lookahead_estimate_indexed) gives survivor c an integer weight wt_c, T is their sum
+// (T < 2^36) and its choice is the first survivor in that order whose inclusive prefix
+// sum of weights exceeds pick_weighted(r, T).
 #pragma once
 
 #include <cstdint>
+
+#if defined(__HIPCC__)
+#include <hip/hip_runtime.h>  // __umul64hi, for the device side of probe_pick_weighted
+#endif
 
 #ifndef TTS_HD
 #if defined(__HIPCC__)
@@ -48,6 +56,14 @@ TTS_HD inline uint64_t probe_draw(uint64_t h, uint32_t level) {
 
 TTS_HD inline uint32_t probe_pick(uint64_t r, uint32_t k) {
   return static_cast<uint32_t>(((r >> 32) * static_cast<uint64_t>(k)) >> 32);
+}
+
+TTS_HD inline uint64_t probe_pick_weighted(uint64_t r, uint64_t T) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  return __umul64hi(r, T);
+#else
+  return static_cast<uint64_t>((static_cast<unsigned __int128>(r) * T) >> 64);
+#endif
 }
 
 }  // namespace tts

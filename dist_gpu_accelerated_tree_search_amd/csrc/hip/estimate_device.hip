@@ -1,4 +1,5 @@
-// Launcher of the device Knuth estimator (estimate_device.hpp, estimate_kernels.hpp).
+// Launcher of the device tree-size estimators, Knuth and lookahead (estimate_device.hpp,
+// estimate_kernels.hpp).
 #include "estimate_device.hpp"
 
 #include <chrono>
@@ -51,17 +52,31 @@ constexpr unsigned kEstLdsLimit = 64u * 1024u;  // what a workgroup gets without
 using Kernel = void (*)(dev::EstParams);
 Kernel pick_kernel(bool lb2) { return lb2 ? dev::knuth_probe_kernel<true> : dev::knuth_probe_kernel<false>; }
 
+using LookKernel = void (*)(dev::LookParams);
+LookKernel pick_look_kernel(bool lb2, bool own) {
+  if (!lb2) return dev::lookahead_probe_kernel<false, true>;
+  return own ? dev::lookahead_probe_kernel<true, true> : dev::lookahead_probe_kernel<true, false>;
+}
+
+dev::EstLds lds_layout(int N, int M, int P, bool lb2, int waves, bool lookahead) {
+  return lookahead ? dev::look_lds_layout(N, M, P, lb2, waves).base : dev::est_lds_layout(N, M, P, lb2, waves);
+}
+
 // Waves per workgroup with which tables and wave state fit the LDS limit: 4, 2 or 1; 0: none.
-int fitting_waves(int N, int M, int P, bool lb2) {
+int fitting_waves(int N, int M, int P, bool lb2, bool lookahead) {
   for (int waves : {dev::kBlock / dev::kWave, 2, 1})
-    if (dev::est_lds_layout(N, M, P, lb2, waves).total <= kEstLdsLimit) return waves;
+    if (lds_layout(N, M, P, lb2, waves, lookahead).total <= kEstLdsLimit) return waves;
   return 0;
 }
 
 }  // namespace
 
-std::string pfsp_estimate_reject(const PfspInstance& in, int lb) {
+std::string pfsp_estimate_reject(const PfspInstance& in, int lb, const EstimateMethod& method) {
   if (lb < 0 || lb > 2) return "lower bound must be 0, 1 or 2";
+  if (method.lookahead) {
+    if (method.power < 1 || method.power > kLookaheadMaxPower) return "lookahead power must be 1, 2 or 3";
+    if (method.look != kLookBoundOwn && method.look != kLookBoundLb1) return "lookahead bound must be own or lb1";
+  }
   if (in.jobs < 1 || in.jobs > kEstimateMaxJobs)
     return "the device estimator takes 1 to " + std::to_string(kEstimateMaxJobs) + " jobs";
   if (in.machines < 2 || in.machines > kEstimateMaxMachines)
@@ -76,17 +91,18 @@ std::string pfsp_estimate_reject(const PfspInstance& in, int lb) {
   if (3 * sum > INT_MAX)
     return "processing times too large for the device estimator: three times their sum must fit 31 bits";
   // the kernel reads its tables from LDS only
-  if (fitting_waves(in.jobs, in.machines, in.npairs, lb == 2) == 0)
+  if (fitting_waves(in.jobs, in.machines, in.npairs, lb == 2, method.lookahead) == 0)
     return "instance too large for the device estimator: its " + std::string(lb == 2 ? "LB2 " : "") +
-           "tables and the state of one wave pass 64 KB of LDS (" + std::to_string(in.jobs) + " jobs x " +
+           "tables and the " + std::string(method.lookahead ? "lookahead " : "") +
+           "state of one wave pass 64 KB of LDS ("+ std::to_string(in.jobs) + " jobs x " +
            std::to_string(in.machines) + " machines)";
   return {};
 }
 
 DeviceEstimate pfsp_device_estimate(const PfspInstance& in, int lb, int best, unsigned long long first_probe,
                                     unsigned long long probes, unsigned long long seed, int device, bool records,
-                                    unsigned long long batch, int max_blocks) {
-  const std::string why = pfsp_estimate_reject(in, lb);
+                                    unsigned long long batch, int max_blocks, const EstimateMethod& method) {
+  const std::string why = pfsp_estimate_reject(in, lb, method);
   if (!why.empty()) throw std::invalid_argument(why);
   if (records && probes > ProbeRecords::kMaxProbes)
     throw std::invalid_argument("probe records are kept for at most 2^20 probes");
@@ -112,14 +128,18 @@ DeviceEstimate pfsp_device_estimate(const PfspInstance& in, int lb, int best, un
 
   // ---- shape of a launch: the most waves per workgroup with which everything fits LDS ----
   DeviceEstimate out;
-  const int waves = fitting_waves(N, M, P, lb2);
-  const dev::EstLds L = dev::est_lds_layout(N, M, P, lb2, waves);
+  const bool look = method.lookahead;
+  const int waves = fitting_waves(N, M, P, lb2, look);
+  const dev::EstLds L = lds_layout(N, M, P, lb2, waves, look);
   const Kernel kernel = pick_kernel(lb2);
+  // LB1's lookahead bound is its own whatever was asked: the LB1 chain
+  const LookKernel look_kernel = pick_look_kernel(lb2, method.look == kLookBoundOwn);
   hipDeviceProp_t prop;
   TTS_HIP_CHECK(hipGetDeviceProperties(&prop, device));
   int per_cu = 0;
-  TTS_HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(kernel),
-                                                             waves * dev::kWave, L.total));
+  TTS_HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(
+      &per_cu, look ? reinterpret_cast<const void*>(look_kernel) : reinterpret_cast<const void*>(kernel),
+      waves * dev::kWave, L.total));
   int max_grid = std::max(1, per_cu) * prop.multiProcessorCount;
   if (max_blocks >= 1) max_grid = std::min(max_grid, max_blocks);
   out.grid = max_grid;
@@ -170,7 +190,11 @@ DeviceEstimate pfsp_device_estimate(const PfspInstance& in, int lb, int best, un
       TTS_HIP_CHECK(hipMemsetAsync(d_rjob.p, 0xff, n * static_cast<size_t>(N) * sizeof(int16_t), stream.s));
     }
     const auto t0 = std::chrono::steady_clock::now();
-    hipLaunchKernelGGL(kernel, dim3(grid), dim3(waves * dev::kWave), L.total, stream.s, a);
+    if (look)
+      hipLaunchKernelGGL(look_kernel, dim3(grid), dim3(waves * dev::kWave), L.total, stream.s,
+                         dev::LookParams{a, method.power});
+    else
+      hipLaunchKernelGGL(kernel, dim3(grid), dim3(waves * dev::kWave), L.total, stream.s, a);
     TTS_HIP_CHECK(hipGetLastError());
     TTS_HIP_CHECK(hipMemcpyAsync(partial.data(), d_partial.p, static_cast<size_t>(grid) * row * sizeof(double),
                                  hipMemcpyDeviceToHost, stream.s));

@@ -1,6 +1,7 @@
 // Device Knuth tree-size estimate for PFSP: the launcher of hip/estimate_kernels.hpp.
 // Probes [first_probe, first_probe + probes) of the host twin (core/estimate.hpp
-// knuth_estimate_indexed), run in bounded launches; the per-workgroup partial sums are
+// knuth_estimate_indexed, or lookahead_estimate_indexed for the lookahead method), run in
+// bounded launches; the per-workgroup partial sums are
 // reduced on the host in (launch, workgroup) order.
 #pragma once
 
@@ -29,8 +30,10 @@ struct DeviceEstimate {
   double seconds = 0;              // all launches, host clock
 };
 
-// Empty when the device estimator accepts (instance, lb); else the reason.
-std::string pfsp_estimate_reject(const PfspInstance& in, int lb);
+// Empty when the device estimator accepts (instance, lb); else the reason. A lookahead
+// probe (method.lookahead, hip/estimate_kernels.hpp lookahead_probe_kernel) keeps a second
+// node, k_c and the weights' prefix sums per wave, so it refuses somewhat smaller instances.
+std::string pfsp_estimate_reject(const PfspInstance& in, int lb, const EstimateMethod& method = {});
 
 // batch 0: the first launch is one pass of the resident grid (one probe per wave, at most
 // kEstimateFirstBatch probes) and is timed; later launches take as many probes as that rate
@@ -45,6 +48,6 @@ constexpr unsigned long long kEstimateMaxBatch = 1ull << 22;
 
 DeviceEstimate pfsp_device_estimate(const PfspInstance& in, int lb, int best, unsigned long long first_probe,
                                     unsigned long long probes, unsigned long long seed, int device, bool records,
-                                    unsigned long long batch, int max_blocks = 0);
+                                    unsigned long long batch, int max_blocks = 0, const EstimateMethod& method = {});
 
 }  // namespace tts

@@ -51,9 +51,17 @@ def progress_weights(model) -> list[float]:
 
 
 def estimate_tree(model, best: int | None = None, probes: int = 1 << 16, seed: int = 1, device: int | None = 0,
-                  first_probe: int = 0, threads: int = 1, records: bool = False, batch: int = 0) -> dict:
+                  first_probe: int = 0, threads: int = 1, records: bool = False, batch: int = 0,
+                  method: str = "knuth", power: int = 2, look: str | None = None) -> dict:
     """Knuth estimate of the tree a PFSP search explores from a fixed incumbent `best`
     (None: model.best_known, the -u 1 tree), from `probes` random root-to-dead-end walks.
+
+    method "knuth": a probe follows a surviving child uniformly. method "lookahead": it
+    follows child c in proportion to (c's own surviving children) ** power, power 1, 2 or
+    3, and reweights, so it never steps into a dead end one level down (unbiased as well,
+    far less skewed; a probe costs about 1 + k child passes per level instead of 1).
+    look is the bound that counts c's children: "own" (the model's) or "lb1"; None is own
+    for lb 0/1 and lb1 for lb 2. power and look are ignored by "knuth" but still checked.
 
     device >= 0: the device estimator (csrc/hip/estimate_kernels.hpp, one wave per probe,
     bounded launches); device None: its host twin on `threads` threads
@@ -61,23 +69,34 @@ def estimate_tree(model, best: int | None = None, probes: int = 1 << 16, seed: i
     the same walk on both, so the two agree probe for probe and differ only in the order
     their sums are added. Returns tree, stderr, depth, probes, per_level (mean estimated
     nodes per level), best, device, seconds, probes_per_s and launch (the device's launch
-    record: probes per launch and the rate that sized them; None on the host), plus
+    record: probes per launch and the rate that sized them; None on the host), method,
+    power and look as used (look resolved), plus
     records (per-probe est, depth, jobs) when asked. N-Queens stays on
     ops.cpu().tree_estimate."""
     if getattr(model, "kind", "pfsp") != "pfsp":
         raise ValueError("estimate_tree is for PFSP models; N-Queens uses ops.cpu().tree_estimate")
+    if method not in ("knuth", "lookahead"):
+        raise ValueError(f"estimate method must be 'knuth' or 'lookahead', not {method!r}")
+    if power not in (1, 2, 3):
+        raise ValueError(f"estimate power must be 1, 2 or 3, not {power!r}")
+    if look is None:
+        look = "lb1" if int(model.lb) == 2 else "own"
+    if look not in ("own", "lb1"):
+        raise ValueError(f"estimate look must be 'own' or 'lb1', not {look!r}")
+    how = dict(method=method, power=int(power), look=look)
     best = int(model.best_known if best is None else best)
     t0 = time.perf_counter()
     if device is None:
         r = dict(ops.cpu().tree_estimate_indexed(model, best, int(probes), int(seed), first_probe=int(first_probe),
-                                                 threads=int(threads), records=bool(records)))
+                                                 threads=int(threads), records=bool(records), **how))
         r["launch"] = None
     else:
         H = ops.require_gpu(device)
         p = model.native.p if hasattr(model, "native") else model.p
         r = dict(H.tree_estimate(int(model.jobs), int(model.machines), [int(x) for x in p], int(model.lb), best,
                                  int(probes), int(seed), first_probe=int(first_probe), device=int(device),
-                                 records=bool(records), batch=int(batch)))
+                                 records=bool(records), batch=int(batch), **how))
+    r.update(how)
     r["seconds"] = time.perf_counter() - t0
     r["probes_per_s"] = r["probes"] / r["seconds"] if r["seconds"] > 0 else float("inf")
     r["best"] = best

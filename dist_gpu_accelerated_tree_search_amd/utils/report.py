@@ -62,10 +62,13 @@ def pfsp_results(optimum: int, tree: int, sol: int, elapsed: float) -> str:
 def pfsp_estimate(inst: int, lb: int, e: dict) -> str:
     """Block of `pfsp --estimate` (search.estimate_tree's dict): tree +- s.e., mean depth, per-level estimates."""
     where = "host twin" if e["device"] is None else f"device {e['device']}"
+    how = "Knuth"
+    if e.get("method", "knuth") != "knuth":
+        how = f"Lookahead (power {e['power']}, look {e['look']})"
     lines = [
         "",
         BANNER,
-        f"Knuth tree-size estimate of ta{inst} ({LB_NAMES.get(lb, 'lb2')}, incumbent {e['best']}) on the {where}",
+        f"{how} tree-size estimate of ta{inst} ({LB_NAMES.get(lb, 'lb2')}, incumbent {e['best']}) on the {where}",
         f"Probes: {e['probes']} in {e['seconds']:.4f} [s] ({e['probes_per_s']:.0f} probes/s)",
         f"Estimated size of the explored tree: {e['tree']:.6g} +- {e['stderr']:.3g} (s.e.)",
         f"Mean probe depth: {e['depth']:.3f}",
