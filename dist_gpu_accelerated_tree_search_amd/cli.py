@@ -17,6 +17,11 @@ pfsp:  -D 0            CPU only: -C threads (0/1 = sequential, ref pfsp_c / pfsp
                            the distributed driver).
                        -w / -L enable work sharing inside a node / across nodes.
        --streams K     K engines per GPU, run concurrently (large trees).
+       --time-limit S  -D 1 -C 0 in one process: stop the device search after S seconds. A
+                       search that did not complete prints, after the results block, its
+                       open nodes, the proven lower bound of the optimum (the smallest
+                       bound of the open pool, engine.pool_bound) and the gap to the best
+                       makespan; --json records gain complete, lower_bound, open_nodes, gap.
        --estimate P    no search: Knuth tree-size estimate of the -u 1 tree from P random
                        probes, on device 0 (-D >= 1) or on the host twin (-D 0, -C threads);
                        --estimate-seed S. Honours --json. --estimate-method lookahead:
@@ -90,6 +95,9 @@ def _pfsp_parser(cls=argparse.ArgumentParser) -> argparse.ArgumentParser:
     ap.add_argument("--estimate-look", choices=["own", "lb1"], default=None,
                     help="bound that counts a child's surviving children for the lookahead weights: the model's own "
                          "or LB1 (default: own for -l 0/1, lb1 for -l 2)")
+    ap.add_argument("--time-limit", type=float, default=None, metavar="S",
+                    help="-D 1 -C 0: stop the device search after S seconds; an unfinished search reports its "
+                         "open nodes, the proven lower bound of the optimum and the gap to the best makespan")
     ap.add_argument("--json", default=None, help="append a JSON run record to this file")
     ap.add_argument("--csv-dir", default=".", help="directory of the CSV statistics files")
     ap.add_argument("--no-csv", action="store_true")
@@ -145,6 +153,13 @@ def _validate_pfsp(a) -> None:
         # RCCL builds one communicator per rank on that rank's own GPU (LOCAL_RANK) and
         # refuses two ranks on one device: ranks pinned to one GPU need the gloo transport
         fail("Error: --device puts every rank on one GPU; use it with --comm gloo")
+    if a.time_limit is not None:
+        # the one-process single-GPU path only (solve_engine): the native runner and the ranks have no limit
+        if (a.D != 1 or a.C != 0 or a.single_process or a.gpus_list or
+                int(os.environ.get("WORLD_SIZE", "1")) != 1):
+            fail("Error: --time-limit needs -D 1 -C 0")
+        if not a.time_limit > 0:
+            fail("Error: --time-limit must be positive")
 
 
 def _steal_cap(a) -> int:
@@ -244,8 +259,10 @@ def pfsp_main(argv: list[str]) -> int:
                                    _init_ub(a, model)))
         eng = model.make_engine("gpu", 0, EngineOptions(max_parents=a.max_parents, ring_bytes=int(a.ring_gb * 2**30),
                                                         streams=max(1, a.streams)))
-        r = solve_engine(model, eng, ub=a.ub, m=a.m, verbose=True)
+        r = solve_engine(model, eng, ub=a.ub, m=a.m, verbose=True, time_limit=a.time_limit)
         print(report.pfsp_results(r.best, r.tree, r.sol, r.elapsed))
+        if not r.complete:
+            print(report.pfsp_time_limit(r.elapsed, r.open_nodes, r.lower_bound, r.best))
         if not a.no_csv:
             w = r.workers[0]
             report.write_single_gpu_csv(os.path.join(a.csv_dir, "singlegpu.csv"), a.inst, a.lb, r.best, a.m, a.M,
@@ -307,7 +324,9 @@ def _json(a, model, r, n_gpus) -> None:
 
         report.write_json_record(a.json, {**model.describe(), "n_gpus": n_gpus, "tree": r.tree, "sol": r.sol,
                                           "best": r.best, "elapsed": r.elapsed, "nodes_per_sec": r.nodes_per_sec,
-                                          "workers": [asdict(w) for w in r.workers], "initial_ub": _init_ub(a, model)})
+                                          "workers": [asdict(w) for w in r.workers], "initial_ub": _init_ub(a, model),
+                                          "complete": r.complete, "lower_bound": r.lower_bound,
+                                          "open_nodes": r.open_nodes, "gap": r.gap})
 
 
 def _init_ub(a, model) -> int | None:

@@ -138,7 +138,29 @@ inline void bind_engine(py::module_& m) {
       .def("fence", &IEngine::fence, py::call_guard<py::gil_scoped_release>(),
            "Wait on the host for every copy enqueued so far.")
       .def("pool_weight", &IEngine::pool_weight, py::arg("w"), py::call_guard<py::gil_scoped_release>(),
-           "Sum over the pool of w[depth] (progress measure, see search.progress_weights).");
+           "Sum over the pool of w[depth] (progress measure, see search.progress_weights).")
+      .def(
+          "pool_bound",
+          [](IEngine& e, int bins) {
+            PoolBound r;
+            {
+              py::gil_scoped_release nogil;
+              r = e.pool_bound(bins);
+            }
+            py::array_t<uint64_t> hist(static_cast<py::ssize_t>(r.hist.size()));
+            std::copy(r.hist.begin(), r.hist.end(), hist.mutable_data());
+            py::dict d;
+            d["lower"] = r.lower;
+            d["cap"] = r.cap;
+            d["nodes"] = r.nodes;
+            d["hist"] = hist;
+            return d;
+          },
+          py::arg("bins") = 64,
+          "What the open pool proves (engine_api.hpp PoolBound): lower = min over the pooled nodes of "
+          "min(own bound, cap), cap = the incumbent, nodes, and hist (uint64): hist[0] stale nodes, hist[k] nodes "
+          "with bound cap - k, the last bin everything at or below cap - (bins - 1). Between runs only; engines "
+          "without a node bound (N-Queens) raise.");
   m.def(
       "make_hybrid_engine",
       [](py::object gpu, py::object cpu, size_t m_, size_t cpu_cap) -> std::unique_ptr<IEngine> {

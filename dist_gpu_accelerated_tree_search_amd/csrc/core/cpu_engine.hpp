@@ -14,6 +14,8 @@
 #include <exception>
 #include <mutex>
 #include <thread>
+#include <type_traits>
+#include <utility>
 #include <vector>
 
 #include "engine_api.hpp"
@@ -21,6 +23,14 @@
 #include "search_cpu.hpp"
 
 namespace tts {
+
+// Problems with a bound of a node itself (pool_bound): int node_bound(const Node&, int cap) const,
+// the node's own bound, exact below cap (at or above cap any value >= cap).
+template <class P, class = void>
+struct has_node_bound : std::false_type {};
+template <class P>
+struct has_node_bound<P, std::void_t<decltype(std::declval<const P&>().node_bound(
+                             std::declval<const typename P::Node&>(), 0))>> : std::true_type {};
 
 template <class Problem>
 class CpuEngine final : public IEngine {
@@ -166,6 +176,22 @@ class CpuEngine final : public IEngine {
     for (size_t i = 0; i < pool_.size(); ++i)
       s += w[std::min<size_t>(static_cast<size_t>(pool_.data()[i].depth), w.size() - 1)];
     return s;
+  }
+  PoolBound pool_bound(int bins) override {
+    if constexpr (has_node_bound<Problem>::value) {
+      join_bg();  // the background batch may reallocate the pool
+      PoolBound r = PoolBound::empty(best_, bins);
+      const size_t n = pool_.size();
+      const Node* nodes = pool_.data();
+      if (threads_ == 1 || n < 4096) {
+        for (size_t i = 0; i < n; ++i) r.add(prob_.node_bound(nodes[i], best_));
+        return r;
+      }
+      pool_bound_fan_out(r, n, threads_, [&](size_t i) { return prob_.node_bound(nodes[i], best_); });
+      return r;
+    } else {
+      return IEngine::pool_bound(bins);
+    }
   }
   EngineStats solve_from(const void* nodes, size_t n, int best) override {
     begin(nodes, n, best);
@@ -372,6 +398,7 @@ class OwningCpuEngine final : public IEngine {
   bool split_pending_known() override { return eng_.split_pending_known(); }
   void offer_best(int b) override { eng_.offer_best(b); }
   double pool_weight(const std::vector<double>& w) override { return eng_.pool_weight(w); }
+  PoolBound pool_bound(int bins) override { return eng_.pool_bound(bins); }
   void set_best(int b) override { eng_.set_best(b); }
   int best() override { return eng_.best(); }
   void reset_counters() override { eng_.reset_counters(); }

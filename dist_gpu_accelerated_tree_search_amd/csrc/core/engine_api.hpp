@@ -6,6 +6,9 @@
 #include <cstddef>
 #include <cstdint>
 #include <functional>
+#include <exception>
+#include <stdexcept>
+#include <thread>
 #include <vector>
 
 namespace tts {
@@ -69,6 +72,80 @@ struct EngineStats {
   // (core/hybrid_engine.hpp); 0 for plain engines
   unsigned long long cpu_tree = 0, cpu_sol = 0;
 };
+
+// What an unfinished search has proved (IEngine::pool_bound). With cap the engine's
+// incumbent, a pooled node counts with b = min(its own bound, cap): the bound of the node
+// itself under the engine's lower bound (LB1 / LB1_d: cpu_lb1 of its prefix, LB2: the
+// full cpu_lb2), not of its children.
+//   lower   min of b over the pool (cap when the pool is empty): the optimum is
+//           >= min(cap, lower), every pruned subtree having had a bound >= the incumbent
+//           of its time, which is >= cap
+//   nodes   pooled nodes (== the sum of hist)
+//   hist    hist[0]: stale nodes (own bound >= cap; the incumbent dropped after they were
+//           pushed, every child of theirs will be pruned); hist[k], 1 <= k < bins - 1:
+//           nodes with b == cap - k; hist[bins - 1]: nodes with b <= cap - (bins - 1)
+struct PoolBound {
+  int lower = 0;
+  int cap = 0;
+  unsigned long long nodes = 0;
+  std::vector<unsigned long long> hist;
+
+  // Counts one node of own bound `own` (callers stop evaluating at cap: own >= cap is stale).
+  void add(int own) {
+    const int b = own < cap ? own : cap;
+    const long long k = static_cast<long long>(cap) - b;
+    const size_t last = hist.size() - 1;
+    ++hist[static_cast<unsigned long long>(k) < last ? static_cast<size_t>(k) : last];
+    ++nodes;
+    if (b < lower) lower = b;
+  }
+  // Folds in the bound of another part of the same pool (same cap, same bins).
+  void merge(const PoolBound& o) {
+    if (o.cap != cap || o.hist.size() != hist.size()) throw std::logic_error("pool_bound: parts disagree on cap or bins");
+    if (o.lower < lower) lower = o.lower;
+    nodes += o.nodes;
+    for (size_t i = 0; i < hist.size(); ++i) hist[i] += o.hist[i];
+  }
+  static PoolBound empty(int cap, int bins) {
+    if (bins < 2) throw std::invalid_argument("pool_bound: bins must be >= 2");
+    PoolBound r;
+    r.lower = r.cap = cap;
+    r.hist.assign(static_cast<size_t>(bins), 0ull);
+    return r;
+  }
+};
+
+// Bounds nodes [0, n) in contiguous shares on `threads` host threads and merges the partial
+// results in thread order into `r`; bound(i) is the own bound of node i. Every started
+// thread is joined on every exit path, and the first exception of a worker (or of a thread
+// that could not start) is rethrown after the joins.
+template <class Bound>
+inline void pool_bound_fan_out(PoolBound& r, size_t n, int threads, Bound&& bound) {
+  const int nt = threads < 1 ? 1 : threads;
+  std::vector<PoolBound> part(static_cast<size_t>(nt), PoolBound::empty(r.cap, static_cast<int>(r.hist.size())));
+  std::vector<std::exception_ptr> err(static_cast<size_t>(nt));
+  {
+    struct Joiner {
+      std::vector<std::thread> th;
+      ~Joiner() {
+        for (auto& x : th)
+          if (x.joinable()) x.join();
+      }
+    } j;
+    j.th.reserve(static_cast<size_t>(nt));
+    for (int t = 0; t < nt; ++t)
+      j.th.emplace_back([&, t]() {
+        try {
+          for (size_t i = n * t / nt; i < n * (t + 1) / nt; ++i) part[t].add(bound(i));
+        } catch (...) {
+          err[t] = std::current_exception();
+        }
+      });
+  }
+  for (auto& e : err)
+    if (e) std::rethrow_exception(e);
+  for (const PoolBound& p : part) r.merge(p);
+}
 
 // Device staging buffers for GPU -> GPU transfers (implemented by the HIP side,
 // csrc/hip/host_support.hpp HipStaging).
@@ -135,6 +212,14 @@ class IEngine {
   // of the search space below a node of depth d, 1 - pool_weight is the explored
   // fraction of the space (the B&B progress measure of tools/progress estimates).
   virtual double pool_weight(const std::vector<double>& w) { (void)w; return 0; }
+  // Proven bound of the open pool (PoolBound above), recomputed node by node; problems
+  // without a node bound (N-Queens) keep this default. Only between runs (a GPU engine
+  // waits for work in flight first, as pool_weight does); the pool, the counters and the
+  // incumbent are left as they are.
+  virtual PoolBound pool_bound(int bins = 64) {
+    (void)bins;
+    throw std::logic_error("this engine has no node bound");
+  }
   // Device timeline of graph replays and pool copies (GPU engines; evidence that the
   // pinned spill/refill overlaps the search): set_trace(true) starts a fresh record,
   // trace() returns {kind, start ms, end ms} triples relative to the first record,

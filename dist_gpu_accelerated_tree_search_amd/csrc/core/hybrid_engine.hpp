@@ -89,6 +89,13 @@ class HybridEngine final : public IEngine {
     c_->reset_counters();
   }
   double pool_weight(const std::vector<double>& w) override { return g_->pool_weight(w) + c_->pool_weight(w); }
+  // (one cap for both parts: the smaller incumbent goes to both first)
+  PoolBound pool_bound(int bins) override {
+    offer_best(best());
+    PoolBound r = g_->pool_bound(bins);
+    r.merge(c_->pool_bound(bins));
+    return r;
+  }
 
   void push_host(const void* nodes, size_t n) override { g_->push_host(nodes, n); }
   size_t pop_host(void* out, size_t max_n) override {

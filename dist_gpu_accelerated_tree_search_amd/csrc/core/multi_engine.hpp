@@ -161,6 +161,14 @@ class MultiEngine final : public IEngine {
     for (auto* x : e_) s += x->pool_weight(w);
     return s;
   }
+  // (one cap for all parts: the smallest incumbent goes to every sub-engine first)
+  PoolBound pool_bound(int bins) override {
+    const int b = best();
+    for (auto* x : e_) x->offer_best(b);
+    PoolBound r = e_[0]->pool_bound(bins);
+    for (size_t i = 1; i < e_.size(); ++i) r.merge(e_[i]->pool_bound(bins));
+    return r;
+  }
   void push_host(const void* nodes, size_t n) override { e_[0]->push_host(nodes, n); }
   size_t pop_host(void* out, size_t max_n) override {
     size_t got = 0;

@@ -215,6 +215,22 @@ struct PfspFrontProblem {
     return lb;
   }
 
+  // Bound of the node itself (IEngine::pool_bound): cpu_lb1 of its prefix, from what the
+  // node carries — the machine-bound chain (cpu_machine_bound) over front + remain of the
+  // unscheduled set + minimum tail, in 32 bits (a u16 front plus a remain may pass 65535).
+  // The root's fronts are the minimum heads. Real machines only, as cpu_lb1.
+  int node_bound(const Node& n, int /*cap*/) const {
+    int r[MB];
+    remain_tail(n, r);  // remain + tail
+    int run = n.front[0] + r[0] - tab.tails[0];
+    int lb = run + tab.tails[0];
+    for (int m = 1; m < inst->machines; ++m) {
+      run = std::max(run, n.front[m] + r[m] - tab.tails[m]);
+      lb = std::max(lb, run + tab.tails[m]);
+    }
+    return lb;
+  }
+
   // Bounds of every child, by job (lb_by_job[j] for j in n.rest).
   void children_bounds(const Node& n, int* lb_by_job) const {
     int r[MB];

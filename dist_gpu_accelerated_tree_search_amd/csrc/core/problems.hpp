@@ -9,6 +9,7 @@
 //          ref nqueens/nqueens_c.c:80-117
 #pragma once
 
+#include <climits>
 #include <cstdint>
 #include <stdexcept>
 
@@ -34,6 +35,12 @@ struct PfspProblem {
     Node r;
     pfsp_init_root(r, inst->jobs);
     return r;
+  }
+
+  // Bound of the node itself (IEngine::pool_bound): LB1 / LB1_d cpu_lb1 of its prefix (the
+  // value its parent computed when it pushed it, LB1 == LB1_d), LB2 the full cpu_lb2.
+  int node_bound(const Node& n, int /*cap*/) const {
+    return lb == 2 ? cpu_lb2(*inst, n.prmu, n.depth, INT_MAX) : cpu_lb1(*inst, n.prmu, n.depth);
   }
 
   template <class Push>

@@ -25,6 +25,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <deque>
+#include <functional>
 #include <memory>
 #include <thread>
 #include <type_traits>
@@ -45,6 +46,12 @@ struct traits_dyn : std::false_type {};
 template <class T>
 struct traits_dyn<T, std::void_t<decltype(T::kDyn)>> : std::bool_constant<T::kDyn> {};
 
+// Traits of a problem with a node bound (PFSP) have a pool_bound launch (below).
+template <class T, class = void>
+struct traits_node_bound : std::false_type {};
+template <class T>
+struct traits_node_bound<T, std::void_t<decltype(&T::pool_bound)>> : std::true_type {};
+
 // Traits contract:
 //   using Node; using Args (with a `PoolArgs<Node> pool` member);
 //   static constexpr int kParentsPerChunk, kChildrenPerChunk, kMaxChunks, kMaxChildren (per parent),
@@ -54,6 +61,9 @@ struct traits_dyn<T, std::void_t<decltype(T::kDyn)>> : std::bool_constant<T::kDy
 //   static void flatten(const dev::PoolArgs<Node>&, int buf, int grid, hipStream_t);
 //   static void finalize(const dev::PoolArgs<Node>&, int buf, int slot, hipStream_t);
 //   static int blocks_per_cu();
+//   static void pool_bound(const Args&, u64 bot, u64 n, int cap, int bins, u64* hist, int* lower, hipStream_t)
+//     (optional, traits_node_bound: adds every node of the ring slice [bot, bot + n) to the
+//     bins of hist and lowers *lower, engine_api.hpp PoolBound);
 template <class Traits>
 class DeviceEngine final : public IEngine, public DeviceResource {
  public:
@@ -488,6 +498,60 @@ class DeviceEngine final : public IEngine, public DeviceResource {
     double host_sum = 0;
     for (const Node& x : host) host_sum += w[std::min<size_t>(static_cast<size_t>(x.depth), w.size() - 1)];
     return dev_sum + host_sum;
+  }
+
+  // The host twin of Traits::pool_bound for the nodes in pinned spill blocks: the own
+  // bound of one node (exact below cap), set by the engine's factory.
+  void set_host_node_bound(std::function<int(const Node&, int)> f) { host_bound_ = std::move(f); }
+
+  PoolBound pool_bound(int bins) override {
+    if constexpr (traits_node_bound<Traits>::value) {
+      if (released_) throw std::runtime_error("engine closed");
+      if (!host_bound_) throw std::logic_error("pool_bound: the engine was built without its host node bound");
+      TTS_HIP_CHECK(hipSetDevice(cfg_.device));
+      settle();
+      normalize();
+      upload_ctl();
+      PoolBound r = PoolBound::empty(h_ctl_->best.v, bins);
+      const size_t n = dev_stack();
+      if (n) {
+        // bins 64-bit counts, then the minimum; freed on every exit path
+        struct Scratch {
+          dev::u64* p = nullptr;
+          ~Scratch() { (void)hipFree(p); }
+        } d;
+        const size_t words = static_cast<size_t>(bins) + 1;
+        TTS_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&d.p), words * sizeof(dev::u64)));
+        std::vector<dev::u64> h(words, 0ull);
+        int* d_lower = reinterpret_cast<int*>(d.p + bins);
+        std::memcpy(&h[bins], &r.cap, sizeof(int));
+        TTS_HIP_CHECK(hipMemcpyAsync(d.p, h.data(), words * sizeof(dev::u64), hipMemcpyHostToDevice, stream_));
+        Traits::pool_bound(args_, static_cast<dev::u64>(h_ctl_->bot), static_cast<dev::u64>(n), r.cap, bins, d.p, d_lower,
+                           stream_);
+        TTS_HIP_CHECK(hipGetLastError());
+        TTS_HIP_CHECK(hipMemcpyAsync(h.data(), d.p, words * sizeof(dev::u64), hipMemcpyDeviceToHost, stream_));
+        TTS_HIP_CHECK(hipStreamSynchronize(stream_));
+        std::memcpy(&r.lower, &h[bins], sizeof(int));
+        for (int i = 0; i < bins; ++i) {
+          r.hist[i] = h[i];
+          r.nodes += h[i];
+        }
+      }
+      std::vector<Node> host;
+      spill_.snapshot(host);
+      // (a spill of millions of nodes: contiguous shares on up to 16 host threads, merged in order)
+      const size_t hn = host.size();
+      const unsigned hw = std::thread::hardware_concurrency();
+      const int nt = hn < 4096 ? 1 : static_cast<int>(std::min<unsigned>(16, std::max<unsigned>(1, hw)));
+      if (nt == 1) {
+        for (const Node& x : host) r.add(host_bound_(x, r.cap));
+        return r;
+      }
+      pool_bound_fan_out(r, hn, nt, [&](size_t i) { return host_bound_(host[i], r.cap); });
+      return r;
+    } else {
+      return IEngine::pool_bound(bins);
+    }
   }
 
   long run(long max_launches, double max_seconds, size_t stop_below) override {
@@ -1278,6 +1342,7 @@ class DeviceEngine final : public IEngine, public DeviceResource {
   std::deque<std::pair<hipEvent_t, size_t>> ahead_;
   hipEvent_t refill_ev_ = nullptr;
   ProgressHook hook_;
+  std::function<int(const Node&, int)> host_bound_;  // set_host_node_bound
   bool released_ = false;          // release(): nothing left to free
   int pending_best_ = 0x7fffffff;  // incumbent handed in by the hook while graphs were in flight
   bool overlap_ = false;           // overlapped rounds (set_overlap)

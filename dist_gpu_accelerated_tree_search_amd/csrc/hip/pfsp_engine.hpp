@@ -22,6 +22,7 @@
 #include "engine.hpp"
 #include "pfsp_front_kernels.hpp"
 #include "pfsp_kernels.hpp"
+#include "pool_bound_kernels.hpp"
 
 namespace tts {
 
@@ -45,6 +46,16 @@ struct PfspTraits {
   }
   static void finalize(const dev::PoolArgs<Node>& pa, int b, int slot, hipStream_t s) {
     hipLaunchKernelGGL((dev::pool_finalize_kernel<Node, G::MAXCHUNKS>), dim3(1), dim3(dev::kBlock), 0, s, pa, b, slot);
+  }
+  // the bound of every ring node (pool_bound_kernels.hpp), for DeviceEngine::pool_bound
+  static void pool_bound(const Args& a, dev::u64 bot, dev::u64 n, int cap, int bins, dev::u64* hist, int* lower,
+                         hipStream_t s) {
+    if constexpr (LBK >= 2)
+      hipLaunchKernelGGL((dev::pool_bound_lb2_kernel<NJ, M>), dim3(dev::bound_blocks(n, dev::kBlock / dev::kWave)),
+                         dim3(dev::kBlock), 0, s, a, bot, n, cap, bins, hist, lower);
+    else
+      hipLaunchKernelGGL((dev::pool_bound_lb1_kernel<NJ, M>), dim3(dev::bound_blocks(n, dev::kBlock)),
+                         dim3(dev::kBlock), 0, s, a, bot, n, cap, bins, hist, lower);
   }
   static int blocks_per_cu() {
     int n = 0;
@@ -97,6 +108,12 @@ struct PfspFrontTraits {
   }
   static void finalize(const dev::PoolArgs<Node>& pa, int b, int slot, hipStream_t s) {
     hipLaunchKernelGGL((dev::pool_finalize_kernel<Node, G::MAXCHUNKS>), dim3(1), dim3(dev::kBlock), 0, s, pa, b, slot);
+  }
+  // the bound of every ring node (pool_bound_kernels.hpp), for DeviceEngine::pool_bound
+  static void pool_bound(const Args& a, dev::u64 bot, dev::u64 n, int cap, int bins, dev::u64* hist, int* lower,
+                         hipStream_t s) {
+    hipLaunchKernelGGL((dev::pool_bound_front_kernel<M, NJ>), dim3(dev::bound_blocks(n, dev::kBlock)),
+                       dim3(dev::kBlock), 0, s, a, bot, n, cap, bins, hist, lower);
   }
   static int blocks_per_cu() {
     // one grid serves both instantiations: what fits of either, capped as measured
@@ -320,6 +337,12 @@ std::unique_ptr<IEngine> make_pfsp_engine_t(const PfspInstance& in, const Engine
   a.lb2_rounds = M >= 10 ? 1 : 0;
   if (const char* f = std::getenv("TTS_LB2_ROUNDS")) a.lb2_rounds = std::atoi(f) != 0;  // A/B runs
   auto eng = std::make_unique<DeviceEngine<PfspTraits<NJ, M, LBK>>>(cfg, a);
+  {  // the host twin of the node bound (spilled nodes): its own copy of the instance
+    auto own = std::make_shared<const PfspInstance>(in);
+    eng->set_host_node_bound([own, prob = PfspProblem<NJ>(*own, LBK >= 2 ? 2 : 1)](const PfspNode<NJ>& n, int cap) {
+      return prob.node_bound(n, cap);
+    });
+  }
   eng->adopt(const_cast<uint16_t*>(a.ptab));
   eng->adopt(const_cast<uint2*>(a.recs));
   eng->adopt(const_cast<uint2*>(a.pinfo));
@@ -334,6 +357,11 @@ std::unique_ptr<IEngine> make_pfsp_front_engine_t(const PfspInstance& in, const 
   const std::vector<uint16_t> ptab = pfsp_front_fill_args(in, a);
   a.ptab = upload_vec(ptab);
   auto eng = std::make_unique<DeviceEngine<PfspFrontTraits<M, NJ>>>(cfg, a);
+  {  // the host twin of the node bound (spilled nodes): its own copy of the instance
+    auto own = std::make_shared<const PfspInstance>(in);
+    auto prob = std::make_shared<const PfspFrontProblem<M, NJ>>(*own, 1);
+    eng->set_host_node_bound([own, prob](const PfspFrontNode<M, NJ>& n, int cap) { return prob->node_bound(n, cap); });
+  }
   eng->adopt(const_cast<uint16_t*>(a.ptab));
   return eng;
 }

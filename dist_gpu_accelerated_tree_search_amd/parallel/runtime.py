@@ -266,6 +266,7 @@ def _rounds(model, engine, comm: Comm, cfg: DistConfig, t_start: float, t_init: 
     elapsed = time.perf_counter() - t_start
     return SolveResult(best=gbest, tree=tree, sol=sol, elapsed=elapsed, t_init=t_init,
                        t_search=t_search, t_tail=0.0, workers=RankTable(cnt, tms, bool(cfg.cpu_workers)),
+                       complete=bool(out["complete"]),  # (stopped early: no pool bound, lower_bound / gap None)
                        extra={"rounds": int(out["rounds"]), "sent_nodes": cnt[:, 2].tolist(),
                               "received_nodes": cnt[:, 3].tolist(), "world": world,
                               "complete": bool(out["complete"]), "dropped_transfers": int(cnt[:, 10].sum()),
@@ -363,6 +364,7 @@ class DistSolver:
         cnt, tms = out["counts"], out["times"]
         return SolveResult(best=int(best), tree=int(tree), sol=int(sol), elapsed=elapsed, t_init=t_init,
                            t_search=t_search, t_tail=0.0, workers=RankTable(cnt, tms, bool(self.cfg.cpu_workers)),
+                           complete=bool(complete),  # (stopped early: no pool bound, lower_bound / gap None)
                            extra={"rounds": int(rounds), "sent_nodes": cnt[:, 2].tolist(),
                                   "received_nodes": cnt[:, 3].tolist(), "world": self.comm.world,
                                   "complete": bool(complete), "dropped_transfers": int(cnt[:, 10].sum()),

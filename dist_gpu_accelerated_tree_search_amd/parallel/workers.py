@@ -53,6 +53,7 @@ def solve_rank(spec: dict) -> dict:
                 res = distributed_solve(model, engine, comm, ub=spec.get("ub", 1), cfg=cfg, window=window)
         out = {"rank": comm.rank, "world": comm.world, "best": res.best, "tree": res.tree, "sol": res.sol,
                "elapsed": res.elapsed, "t_init": res.t_init, "t_search": res.t_search, "extra": res.extra,
+               "complete": res.complete, "lower_bound": res.lower_bound, "open_nodes": res.open_nodes, "gap": res.gap,
                "workers": [asdict(w) for w in res.workers],
                "comm": {"device_transfers": comm.device_transfers, "host_transfers": comm.host_transfers,
                         "bytes_sent": comm.bytes_sent, "bytes_recv": comm.bytes_recv}}

@@ -19,6 +19,8 @@ from . import ops
 from .models.pfsp import EngineOptions
 from .utils.report import WorkerStats
 
+INT_MAX = 2**31 - 1
+
 
 @dataclass
 class SolveResult:
@@ -31,10 +33,31 @@ class SolveResult:
     t_tail: float = 0.0
     workers: list = field(default_factory=list)
     extra: dict = field(default_factory=dict)
+    # a time-limited solve that stopped with nodes still pooled (solve_engine time_limit):
+    # complete False, open_nodes the pool left in the engine, lower_bound what the search
+    # has proved (optimum >= lower_bound; a complete solve: == best). A run stopped early
+    # without a pool bound (ranks under DistConfig time_limit_s / max_rounds): complete
+    # False, lower_bound and gap None
+    complete: bool = True
+    lower_bound: int | None = None
+    open_nodes: int = 0
+
+    def __post_init__(self):
+        if self.complete and self.lower_bound is None:
+            self.lower_bound = self.best
 
     @property
     def nodes_per_sec(self) -> float:
         return self.tree / self.elapsed if self.elapsed > 0 else float("inf")
+
+    @property
+    def gap(self) -> float | None:
+        """(best - lower_bound) / best: 0.0 when complete, None while no schedule is known."""
+        if self.complete:
+            return 0.0
+        if self.best >= INT_MAX or self.lower_bound is None:
+            return None
+        return (self.best - self.lower_bound) / self.best
 
 
 def progress_weights(model) -> list[float]:
@@ -121,11 +144,19 @@ def solve_cpu(model, ub: int = 1, threads: int = 0, m: int = 25, batch: int = 20
 
 
 def solve_engine(model, engine, ub: int = 1, m: int = 25, best: int | None = None,
-                 verbose: bool = False) -> SolveResult:
+                 verbose: bool = False, time_limit: float | None = None) -> SolveResult:
     """One complete solve on an existing engine (GPU or CPU backend).
 
     The engine is reused across solves (allocation and graph capture are setup,
-    like model initialisation); its counters are reset here."""
+    like model initialisation); its counters are reset here.
+
+    time_limit (seconds, PFSP): the engine search stops after it. If nodes remain, the
+    host drain is skipped and the pool stays in the engine — the caller may resume with
+    engine.run — and the result is complete False with open_nodes, lower_bound (min of
+    the incumbent and engine.pool_bound()["lower"]: the optimum is proved >= it) and gap;
+    extra["pool_bound"] holds the whole pool_bound dict."""
+    if time_limit is not None and not time_limit > 0:
+        raise ValueError("time_limit must be positive")
     t0 = time.perf_counter()
     best = model.search_best(ub) if best is None else best
     nodes, tree1, sol1, best = model.warmup(best, m)
@@ -133,7 +164,12 @@ def solve_engine(model, engine, ub: int = 1, m: int = 25, best: int | None = Non
     if verbose:
         from .utils.report import phase
         print(phase("Initial search on CPU completed", tree1, sol1, t1 - t0))
-    st = engine.solve(nodes, int(best))  # reset + load + run to exhaustion, one native call
+    if time_limit is None:
+        st = engine.solve(nodes, int(best))  # reset + load + run to exhaustion, one native call
+    else:
+        engine.begin(nodes, int(best))
+        engine.run(-1, float(time_limit), 0)
+        st = engine.stats()
     launches = st["launches"]
     best = min(best, st["best"])
     t2 = time.perf_counter()
@@ -142,28 +178,45 @@ def solve_engine(model, engine, ub: int = 1, m: int = 25, best: int | None = Non
         print(phase("Search on GPU completed", tree, sol, t2 - t1))
     # Step 3: the engine drains completely; anything left (none) goes to the host
     left = engine.size()
-    if left:
+    bound = None
+    if left and time_limit is not None:
+        bound = engine.pool_bound()
+    elif left:
         rest = engine.pop(left)
         tr, so, best = model.drain(best, rest)
         tree += tr
         sol += so
     t3 = time.perf_counter()
     if verbose:
-        print(phase("Final on CPU completed", tree, sol, t3 - t2))
-        print("\nExploration terminated.")
+        if bound is None:
+            print(phase("Final on CPU completed", tree, sol, t3 - t2))
+            print("\nExploration terminated.")
+        else:  # (no host drain: the pool stays in the engine)
+            print("\nExploration stopped.")
     w = WorkerStats(tree=st["tree"], sol=st["sol"], gen_child=st["tree"], t_memcpy=st["t_memcpy"],
                     t_malloc=st["t_malloc"], t_kernel=st["t_run"])
-    return SolveResult(best=best, tree=tree, sol=sol, elapsed=t3 - t0, t_init=t1 - t0, t_search=t2 - t1,
-                       t_tail=t3 - t2, workers=[w], extra={"launches": launches, "iters": st["iters"],
-                                                           "parents": st["parents"], "syncs": st["syncs"]})
+    r = SolveResult(best=best, tree=tree, sol=sol, elapsed=t3 - t0, t_init=t1 - t0, t_search=t2 - t1,
+                    t_tail=t3 - t2, workers=[w], extra={"launches": launches, "iters": st["iters"],
+                                                        "parents": st["parents"], "syncs": st["syncs"]})
+    if bound is not None:
+        r.complete = False
+        r.open_nodes = int(left)
+        r.lower_bound = min(int(best), int(bound["lower"]))
+        r.extra["pool_bound"] = bound
+    return r
 
 
 def solve_gpu(model, ub: int = 1, device: int = 0, m: int = 25, opts: EngineOptions | None = None,
-              verbose: bool = False) -> SolveResult:
-    """Single-GPU solve (ref pfsp_multigpu_cuda.c with -D 1 -C 0)."""
+              verbose: bool = False, time_limit: float | None = None) -> SolveResult:
+    """Single-GPU solve (ref pfsp_multigpu_cuda.c with -D 1 -C 0). time_limit: see
+    solve_engine; an incomplete result keeps its engine in extra["engine"] (the open pool
+    lives there: engine.run resumes it, engine.pool_bound re-evaluates it)."""
     eng = model.make_engine("gpu", device, opts)
     try:
-        return solve_engine(model, eng, ub=ub, m=m, verbose=verbose)
+        r = solve_engine(model, eng, ub=ub, m=m, verbose=verbose, time_limit=time_limit)
+        if not r.complete:
+            r.extra["engine"] = eng
+        return r
     finally:
         del eng
 

@@ -59,6 +59,21 @@ def pfsp_results(optimum: int, tree: int, sol: int, elapsed: float) -> str:
     ])
 
 
+def pfsp_time_limit(elapsed: float, open_nodes: int, lower: int, best: int | None) -> str:
+    """Block of `pfsp --time-limit` after a search that did not complete: what it has proved
+    (search.SolveResult lower_bound / gap). best None or INT_MAX: no schedule found yet."""
+    if best is None or best >= 2**31 - 1:
+        gap = "Gap to best makespan: unknown (no schedule found)"
+    else:
+        gap = "Gap to best makespan: %.2f %%" % (100.0 * (best - lower) / best)
+    return "\n".join([
+        "Time limit reached after %.4f s: exploration not completed." % elapsed,
+        "Open nodes: %d" % open_nodes,
+        "Proven lower bound: %d" % lower,
+        gap,
+    ])
+
+
 def pfsp_estimate(inst: int, lb: int, e: dict) -> str:
     """Block of `pfsp --estimate` (search.estimate_tree's dict): tree +- s.e., mean depth, per-level estimates."""
     where = "host twin" if e["device"] is None else f"device {e['device']}"
